@@ -2,7 +2,7 @@
 """Benchmark of the APPLES per-query hot path on MI355X (BASELINE.json's metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c4|c5|c3-clustered|c4-clustered|small]
-                    [--scaling weak|strong] [--no-cpu] [--queries Q]
+                    [--scaling weak|strong] [--queries Q] [--dump-outputs DIR] [--full [--no-cpu] [--no-extras]]
 
 Default workload = BASELINE.json config 3, the one the targets are quoted on: synthetic 200 k-leaf
 backbone, L = 1000 nt, 100 k queries, OLS/JC69, -f 0.2 -b 25.
@@ -13,8 +13,15 @@ arrays in host memory (the reference's S1 arrays) and the step ends when the pla
 host memory -- upload, packing into the device layouts, distance vector, observed-set selection,
 least-squares sweep, best edge, copy back (apples_place_from_sequences).  The packed reference
 alignment and the tree are resident in HBM (the reference's workers likewise hold them before the
-timer starts).  value = query placements/s for the whole job.  `resident` in the JSON line is the
-same pass with the query block already uploaded and packed (device time only).
+timer starts).  value = query placements/s for the whole job, ms_per_step = the milliseconds one timed step took.
+
+A plain run sets up, warms up, times --steps steps, writes the last timed step's placements if --dump-outputs DIR is
+given (one DIR/<field>.npy per field of the placement structs, float64, in query order: what a caller of the timed
+path receives; the inputs are seeded, so two builds can be compared array for array; beyond 64 MB in all, a fixed
+seeded sample of the queries with their indices in query_index.npy) and prints the line with the
+`roofline` of the dominant kernel from the timed steps' own HIP-event times.  Everything that takes runs of its own
+is behind --full: `resident` (the same pass with the query block already uploaded and packed, device time only, with
+the check that it delivers the timed path's bytes) and the legs listed below.
 
 For N > 1 there is one rank process per GPU: `python bench.py --gpus N` starts them itself (a parent that never
 touches a device spawns N fresh interpreters with RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set and relays rank
@@ -27,7 +34,7 @@ GPUs"): the workload's queries are split over the ranks; --scaling weak (default
 block of the workload's size.  Fewer visible devices than ranks is an error, not an oversubscription.
 
 Prints ONE JSON line on rank 0 with `roofline` (dominant kernel, algorithmic bytes or operations /
-HIP-event time), `roofline_hbm_point` (BASELINE.json's second figure: the distance kernel at one
+HIP-event time) and, with --full, `resident`, `roofline_hbm_point` (BASELINE.json's second figure: the distance kernel at one
 query per pass over a packed reference larger than every cache, streamed from HBM for several seconds after the
 timed region), `distance_kernel_stream` (the same kernel on the workload's own reference, which the Infinity
 Cache holds: the cache figure), `strong_scaling_proxy` (the 8-GPU shards of the query set timed one by one on
@@ -540,6 +547,18 @@ def load_traffic(workload, kernel):
         return None, None
 
 
+DUMP_MAX_BYTES = 64 * 10 ** 6  # what --dump-outputs may write in all
+
+
+def dump_sample(n_rows, n_fields, max_bytes=DUMP_MAX_BYTES):
+    """None where n_fields float64 arrays of n_rows values fit into max_bytes; otherwise the sorted indices of a fixed,
+    seeded sample of the rows, as many as fit beside the index array itself."""
+    if 8 * n_fields * n_rows <= max_bytes:
+        return None
+    keep = max_bytes // (8 * (n_fields + 1))
+    return np.sort(np.random.default_rng(64).choice(n_rows, size=keep, replace=False))
+
+
 def make_clusters(ds, threshold, protein=False):
     """Clusters + consensus rows of the command line's default route (run_apples.py: max-diameter
     clusters at 1.2 x -f, apples/Reference.py:87; the consensus over the alphabet of apples/PoolRepresentativeWorker.py:33-58)."""
@@ -559,18 +578,28 @@ def main():
     ap.add_argument('--scaling', default='', choices=['', 'weak', 'strong'],
                     help="strong: the workload's queries are split over the ranks (default for c3 = BASELINE config 3); "
                          'weak: every rank places a block of the workload\'s size (default for the other workloads)')
-    ap.add_argument('--no-cpu', action='store_true', help='skip the CPU baseline leg')
+    ap.add_argument('--dump-outputs', metavar='DIR', default='',
+                    help="after the timed steps, write the last timed step's placements (the whole job's, as rank 0 holds them) "
+                         'as DIR/<field>.npy, one float64 array per field of the placement structs, in query order')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, also run what the headline figure does not need: the resident pass and its check '
+                         'against the timed path, the distance-kernel stream point, the CPU baseline, the HBM point, the '
+                         'strong-scaling proxy, the clustered route, the other workloads and input shapes')
+    ap.add_argument('--no-cpu', action='store_true', help='with --full: skip the CPU baseline leg')
     ap.add_argument('--queries', type=int, default=0, help='override the number of queries (per GPU when weak)')
     ap.add_argument('--gather', default='rccl', choices=['torch', 'rccl'],
                     help='the end-of-run gather for N > 1: ctypes on librccl.so without PyTorch (apples_amd/rccl.py, default) '
                          'or torch.distributed (backend nccl = RCCL)')
     ap.add_argument('--no-extras', action='store_true',
-                    help='skip the untimed extras of the N = 1 line (HBM point, strong-scaling proxy, clustered route)')
+                    help='with --full: skip the extras of the N = 1 line (HBM point, strong-scaling proxy, clustered route, '
+                         'other workloads and input shapes)')
     ap.add_argument('--timed', default='', choices=['', 'host', 'resident'],
                     help='what a step covers: host = host buffers in, placements in host memory (default for alignment '
                          'workloads); resident = inputs already uploaded (default for c5: a 200 k-column table block is '
                          'gigabytes over PCIe, which is the copy and not the path)')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
     if not args.scaling:
         args.scaling = 'strong' if args.workload == 'c3' else 'weak'
 
@@ -709,30 +738,43 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
 
-    # untimed: the resident form (query block / table already uploaded and packed; device time only)
-    if res_handle is not None:
-        handle = res_handle
-    elif table:
-        handle, _ = eng.upload_table(D, nodes)
-    else:
-        handle, _ = eng.upload_queries(queries)
-    eng.place_resident(handle)
-    sync()
-    t1 = time.perf_counter()
-    res_phases = {'dist_ms': 0.0, 'select_ms': 0.0, 'sweep_ms': 0.0}
-    for _ in range(args.steps):
-        eng.place_resident(handle)
-        t = eng.timing()
-        for k in res_phases:
-            res_phases[k] += t[k]
-    dt_res = time.perf_counter() - t1
+    if rank == 0 and args.dump_outputs:
+        # what the last timed step returned, field by field (the int32 / uint32 fields are exact in float64)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        picked = dump_sample(len(out), len(PLACEMENT_DTYPE.names))
+        if picked is not None:  # more than DUMP_MAX_BYTES: a fixed, seeded sample of the queries, with their indices
+            np.save(os.path.join(args.dump_outputs, 'query_index.npy'), picked.astype(np.float64))
+        for name in PLACEMENT_DTYPE.names:
+            np.save(os.path.join(args.dump_outputs, name + '.npy'),
+                    np.ascontiguousarray(out[name] if picked is None else out[name][picked], dtype=np.float64))
+
     final_line = None
-    mine = eng.fetch(handle, nq)
-    eng.free_queries(handle)
-    if rank == 0:
-        mine0 = out[:nq]
-        if mine0.tobytes() != mine.tobytes():
+    mine = out[:nq] if rank == 0 else None  # this rank's own placements
+    if args.full:
+        # untimed: the resident form (query block / table already uploaded and packed; device time only)
+        if res_handle is not None:
+            handle = res_handle
+        elif table:
+            handle, _ = eng.upload_table(D, nodes)
+        else:
+            handle, _ = eng.upload_queries(queries)
+        eng.place_resident(handle)
+        sync()
+        t1 = time.perf_counter()
+        res_phases = {'dist_ms': 0.0, 'select_ms': 0.0, 'sweep_ms': 0.0}
+        for _ in range(args.steps):
+            eng.place_resident(handle)
+            t = eng.timing()
+            for k in res_phases:
+                res_phases[k] += t[k]
+        dt_res = time.perf_counter() - t1
+        mine = eng.fetch(handle, nq)
+        eng.free_queries(handle)
+        if rank == 0 and out[:nq].tobytes() != mine.tobytes():
             raise SystemExit('bench: the host-buffer pass and the resident pass disagree')
+    elif res_handle is not None:
+        eng.free_queries(res_handle)
+    if rank == 0:
         total_q = int(sum(sizes))
         ms_per_step = dt / args.steps * 1e3
         value = total_q / (dt / args.steps)
@@ -744,15 +786,14 @@ def main():
         roofline = roofline_of(args.workload, nq, rows, L, protein, table, per_step, launches / args.steps, mine, info,
                                filter_ms=phases['filter_ms'] / args.steps)
         stream = proxy = None
-        if world == 1 and not table and not protein and not clustered:
+        if args.full and world == 1 and not table and not protein and not clustered:
             stream = distance_stream_point(eng, ds, L)
-        extras = world == 1 and not args.no_extras and not use_dist
+        extras = args.full and world == 1 and not args.no_extras and not use_dist
         if extras and args.workload == 'c3':
             proxy = strong_scaling_proxy(eng, queries, ms_per_step, device=local_rank, full=mine)
         cpu = None
-        if world == 1 and not args.no_cpu and not clustered:
+        if args.full and world == 1 and not args.no_cpu and not clustered:
             cpu = cpu_baseline_table(ds, D, method, thr) if table else cpu_baseline(ds, protein, method, thr)
-        res_ms = dt_res / args.steps * 1e3
         line = {
             'metric': 'query placements/sec (whole node)', 'value': value, 'unit': 'queries/s',
             'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': ms_per_step,
@@ -774,12 +815,13 @@ def main():
                        'placements_crc32': zlib.crc32(np.ascontiguousarray(out).tobytes()),
                        'gather': ('librccl via ctypes (no PyTorch)' if comm is not None else 'torch.distributed nccl') if use_dist else None},
             'roofline': roofline,
-            'resident': {'value': world * nq / (dt_res / args.steps), 'ms_per_step': res_ms, 'unit': 'queries/s',
-                         'per_kernel_ms_per_step': {k: v / args.steps for k, v in res_phases.items()},
-                         'note': 'same pass, query block already uploaded and packed (rank 0, device time only)'},
-            'distance_kernel_stream': stream,
-            'cpu_baseline': cpu,
         }
+        if args.full:
+            line['resident'] = {'value': world * nq / (dt_res / args.steps), 'ms_per_step': dt_res / args.steps * 1e3, 'unit': 'queries/s',
+                                'per_kernel_ms_per_step': {k: v / args.steps for k, v in res_phases.items()},
+                                'note': 'same pass, query block already uploaded and packed (rank 0, device time only)'}
+            line['distance_kernel_stream'] = stream
+            line['cpu_baseline'] = cpu
         if cpu:
             line['speedup_vs_cpu_baseline'] = value / cpu['value']
         if proxy:

@@ -10,7 +10,7 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 stats() {  # name, bench args...
   name=$1; shift
-  timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_$name -- python3 $R/bench.py --no-cpu --no-extras "$@" > $OUT/bench_${name}_under_rocprof.json 2> $OUT/stats_$name.log
+  timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_$name -- python3 $R/bench.py --full --no-cpu --no-extras "$@" > $OUT/bench_${name}_under_rocprof.json 2> $OUT/stats_$name.log
   cp $(ls $OUT/stats_$name/*/*kernel_stats.csv | head -1) $OUT/${name}_kernel_stats.csv
   rm -rf $OUT/stats_$name
 }
@@ -23,7 +23,7 @@ stats c4_clustered --workload c4-clustered --steps 3 --warmup 1
 cd $R
 for W in c3 c2 c4 c5 c3-clustered c4-clustered; do
   # (the whole workload: the launch shape -- queries per device batch -- must be the bench's own)
-  bash scripts/pmc_traffic_passes.sh $TAG/pmc_$W --workload $W --no-extras --steps 1 --warmup 1 > /dev/null 2>&1
+  bash scripts/pmc_traffic_passes.sh $TAG/pmc_$W --workload $W --full --no-extras --steps 1 --warmup 1 > /dev/null 2>&1
   python scripts/pmc_to_traffic.py gpurun_out/$TAG/pmc_$W $W $OUT/pmc_traffic.json > /dev/null
   rm -rf gpurun_out/$TAG/pmc_$W
 done
@@ -35,12 +35,12 @@ for w in d:
 json.dump(d, open('$OUT/pmc_traffic.json', 'w'), indent=1, sort_keys=True)
 PY
 cp $OUT/pmc_traffic.json profiles/pmc_summary.json
-python bench.py --steps 20 --warmup 5 2> $OUT/bench_c3.log | tail -1 > $OUT/bench_c3.json
-python bench.py --workload c2 --steps 20 --warmup 5 2> $OUT/bench_c2.log | tail -1 > $OUT/bench_c2.json
-python bench.py --workload c4 --steps 3 --warmup 1 2> $OUT/bench_c4.log | tail -1 > $OUT/bench_c4.json
-python bench.py --workload c5 --steps 5 --warmup 2 2> $OUT/bench_c5.log | tail -1 > $OUT/bench_c5.json
-python bench.py --workload c3-clustered --steps 3 --warmup 1 --no-cpu 2> $OUT/bench_c3cl.log | tail -1 > $OUT/bench_c3cl.json
-python bench.py --workload c4-clustered --steps 3 --warmup 1 --no-cpu 2> $OUT/bench_c4cl.log | tail -1 > $OUT/bench_c4cl.json
+python bench.py --full --steps 20 --warmup 5 2> $OUT/bench_c3.log | tail -1 > $OUT/bench_c3.json
+python bench.py --full --workload c2 --steps 20 --warmup 5 2> $OUT/bench_c2.log | tail -1 > $OUT/bench_c2.json
+python bench.py --full --workload c4 --steps 3 --warmup 1 2> $OUT/bench_c4.log | tail -1 > $OUT/bench_c4.json
+python bench.py --full --workload c5 --steps 5 --warmup 2 2> $OUT/bench_c5.log | tail -1 > $OUT/bench_c5.json
+python bench.py --full --workload c3-clustered --steps 3 --warmup 1 --no-cpu 2> $OUT/bench_c3cl.log | tail -1 > $OUT/bench_c3cl.json
+python bench.py --full --workload c4-clustered --steps 3 --warmup 1 --no-cpu 2> $OUT/bench_c4cl.log | tail -1 > $OUT/bench_c4cl.json
 python scripts/r05_hybrid_probe.py > $OUT/hybrid_c3.json 2> $OUT/hybrid_c3.log
 # the check the bench line's per-step fields promise: the dominant kernel's total time in the trace / the passes traced == the line's
 # dominant_kernel_ms_per_step (the traced command runs steps + warmup host passes and steps + 1 resident ones)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """The legs of config 3's size in the shapes real inputs have (bench.py: variant_dataset / other_shapes), one by one, each
-inside its own try: what `python bench.py` adds to its line as `other_shapes`, without the rest of the line.
+inside its own try: what `python bench.py --full` adds to its line as `other_shapes`, without the rest of the line.
 
     python scripts/shape_legs.py [leg ...] > gpurun_out/shape_legs.json
 """

@@ -55,6 +55,16 @@ def test_roofline_of_table_input_and_sweep_bound_workloads():
     assert abs(r['achieved'] - 332.0 * 399999 * 2048 / 51.0e-3 / 1e9) < 1e-3
 
 
+def test_dump_sample_keeps_the_dumped_outputs_within_their_cap():
+    assert bench.dump_sample(100000, 7) is None  # config 3: 5.6 MB, every query
+    assert bench.dump_sample(bench.DUMP_MAX_BYTES // 56, 7) is None
+    n = 3000000
+    idx = bench.dump_sample(n, 7)
+    assert 8 * (7 + 1) * len(idx) <= bench.DUMP_MAX_BYTES < 8 * (7 + 1) * (len(idx) + 1)
+    assert np.all(np.diff(idx) > 0) and 0 <= idx[0] and idx[-1] < n
+    assert np.array_equal(idx, bench.dump_sample(n, 7))  # the same sample from run to run
+
+
 def test_committed_counter_summary_names_every_workload_and_one_commit():
     d = json.load(open(os.path.join(ROOT, 'profiles', 'pmc_summary.json')))
     assert set(d) >= {'c2', 'c3', 'c4', 'c5', 'c3-clustered'}

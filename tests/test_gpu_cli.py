@@ -96,13 +96,14 @@ def test_bench_gather_through_librccl_without_torch():
     env = dict(os.environ, APPLES_BENCH_FORCE_DIST='1', HSA_ENABLE_IPC_MODE_LEGACY='0', RANK='0', LOCAL_RANK='0',
                WORLD_SIZE='1', MASTER_ADDR='127.0.0.1', MASTER_PORT='29541')
     code = ("import sys, runpy; sys.argv = ['bench.py', '--gpus', '1', '--steps', '2', '--warmup', '1', '--workload', 'small',"
-            " '--no-cpu', '--gather', 'rccl']\n"
+            " '--full', '--no-cpu', '--gather', 'rccl']\n"
             "runpy.run_path(%r, run_name='__main__')\n"
             "assert 'torch' not in sys.modules, 'PyTorch was imported'\n" % os.path.join(ROOT, 'bench.py'))
     r = subprocess.run([sys.executable, '-c', code], capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
     assert line['n_gpus'] == 1 and line['value'] > 0 and 'librccl' in line['config']['gather']
+    assert line['resident']['value'] > 0  # --full: bench.py itself compared the gathered bytes with what the device buffer holds
     assert r.stdout.strip().splitlines()[-1].startswith('{')  # the JSON line is the last thing on stdout
 
 
@@ -115,7 +116,7 @@ def test_bench_multi_rank_path_on_one_gpu(scaling):
     env = dict(os.environ, APPLES_BENCH_FORCE_DIST='1', HSA_ENABLE_IPC_MODE_LEGACY='0')
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '1', '--master-addr',
            '127.0.0.1', '--master-port', '29533' if scaling == 'weak' else '29534', os.path.join(ROOT, 'bench.py'),
-           '--gpus', '1', '--steps', '2', '--warmup', '1', '--workload', 'small', '--no-cpu', '--scaling', scaling]
+           '--gpus', '1', '--steps', '2', '--warmup', '1', '--workload', 'small', '--full', '--no-cpu', '--scaling', scaling]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
@@ -144,13 +145,43 @@ def test_bench_two_ranks_when_two_gpus():
     crc = {}
     for n in (1, 2):
         r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', str(n), '--steps', '2', '--warmup', '1', '--workload',
-                            'small', '--no-cpu', '--no-extras', '--scaling', 'strong', '--gather', 'rccl'],
+                            'small', '--full', '--no-cpu', '--no-extras', '--scaling', 'strong', '--gather', 'rccl'],
                            capture_output=True, text=True, timeout=900, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY='0'))
         assert r.returncode == 0, r.stderr[-2000:]
         line = json.loads(r.stdout.strip().splitlines()[-1])
         assert line['n_gpus'] == n and line['config']['queries_total'] == 2048
         crc[n] = line['config']['placements_crc32']
     assert crc[1] == crc[2]
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain `bench.py` run times its steps and nothing else (the legs with runs of their own are behind --full);
+    --dump-outputs writes the last timed step's placements, one float64 array per field of the placement structs,
+    the same arrays from run to run, and they are the bytes the line's checksum is taken of."""
+    import zlib
+    import numpy as np
+    from apples_amd.engine import PLACEMENT_DTYPE
+    dumps = []
+    for k, steps in enumerate((3, 1)):
+        d = tmp_path / ('dump%d' % k)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', str(steps), '--warmup', '1',
+                            '--workload', 'small', '--dump-outputs', str(d)], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads(r.stdout.strip().splitlines()[-1])
+        assert line['steps'] == steps and line['value'] > 0 and line['unit'] == 'queries/s' and line['higher_is_better'] is True
+        assert line['ms_per_step'] == pytest.approx(2048 / line['value'] * 1e3, rel=1e-9)
+        assert line['roofline']['frac'] > 0
+        for moved in ('resident', 'cpu_baseline', 'distance_kernel_stream', 'roofline_hbm_point', 'clustered', 'other_workloads'):
+            assert moved not in line
+        assert sorted(os.listdir(d)) == sorted(n + '.npy' for n in PLACEMENT_DTYPE.names)
+        arrays = {n: np.load(d / (n + '.npy')) for n in PLACEMENT_DTYPE.names}
+        assert all(a.dtype == np.float64 and a.shape == (2048,) for a in arrays.values())
+        back = np.zeros(2048, dtype=PLACEMENT_DTYPE)
+        for n in PLACEMENT_DTYPE.names:
+            back[n] = arrays[n]
+        assert zlib.crc32(back.tobytes()) == line['config']['placements_crc32']
+        dumps.append(back.tobytes())
+    assert dumps[0] == dumps[1]
 
 
 def test_cli_reference_alignment_with_rows_beyond_the_tree(tmp_path):

@@ -1,7 +1,7 @@
 """Backbone branch re-estimation wrapper (apples_amd/reestimate.py; apples/reestimateBackbone.py:22-118):
 polytomy resolution, Newick round trip, re-rooting FastTree's unrooted answer on the input's root edge.
-FastTree itself is external: a stand-in script here, the reference's bundled binary when this container
-has it."""
+FastTree itself is external: a stand-in script here, and the recorded answers of the binary the reference
+bundles (tests/golden/g9_fasttree_*.nwk), replayed by an executable that checks what it is given."""
 import os
 import stat
 import sys
@@ -129,15 +129,38 @@ def test_wrapper_with_a_stand_in_fasttree(tmp_path, monkeypatch):
         assert got[k] == pytest.approx(2 * want[k], rel=1e-12)
 
 
-BUNDLED = '/root/reference/apples/tools/FastTree-linux'
+def _bipartitions(root):
+    """The splits of a tree whichever side is below and wherever the root is: the smaller side of every edge."""
+    every = frozenset(x.label for x in root.leaves())
+    return {min(s, every - s, key=lambda x: (len(x), sorted(x))) for s in _splits(root)}
 
 
-@pytest.mark.skipif(not os.path.exists(BUNDLED), reason='the reference tree (with its bundled FastTree) is only in the build container')
-def test_wrapper_with_the_bundled_fasttree_on_the_example_data():
-    """End to end on data/backbone.nwk + data/ref.fa with the FastTree the reference ships: same leaf set,
+def _bundled_fasttree(tmp_path, recording, ref_fp):
+    """The FastTree the reference ships (apples/tools/FastTree-linux, 2.1.11), replayed: an executable that checks it is
+    run with the reference's flags (and the wrapper's -log), on the alignment and the topology the recording was made from
+    (tests/golden/g9_*, written by that binary without -log, which changes no output: tests/golden/make_goldens.py g9), and
+    prints what the binary printed."""
+    exe = tmp_path / 'FastTree-replay'
+    with open(exe, 'w') as f:
+        f.write('#!%s\nimport sys\nsys.path.insert(0, %r); sys.path.insert(0, %r)\n'
+                'from apples_amd import reestimate as R\nfrom test_reestimate import _bipartitions\n'
+                'a = sys.argv\nassert "-nosupport" in a and "-nome" in a and "-noml" in a and "-nt" in a and "-log" in a\n'
+                'assert sys.stdin.read() == open(%r).read()\n'
+                'text = open(%r).read()\n'
+                'given, made = R.from_newick(open(a[a.index("-intree") + 1]).read()), R.from_newick(text)\n'
+                'assert sorted(x.label for x in given.leaves()) == sorted(x.label for x in made.leaves())\n'
+                'assert _bipartitions(given) == _bipartitions(made)\n'
+                'sys.stdout.write(text)\n' % (sys.executable, ROOT, os.path.join(ROOT, 'tests'), str(ref_fp), str(recording)))
+    os.chmod(exe, os.stat(exe).st_mode | stat.S_IEXEC)
+    return str(exe)
+
+
+def test_wrapper_with_the_bundled_fasttree_on_the_example_data(tmp_path, golden_dir):
+    """End to end on data/backbone.nwk + data/ref.fa with the answer of the FastTree the reference ships: same leaf set,
     same splits (the topology is fixed by -intree), same root edge, finite lengths, and the result is a
     tree this build's reader and the placement path accept."""
-    o = _options(os.path.join(DATA, 'backbone.nwk'), os.path.join(DATA, 'ref.fa'), BUNDLED)
+    exe = _bundled_fasttree(tmp_path, os.path.join(golden_dir, 'g9_fasttree_data.nwk'), os.path.join(DATA, 'ref.fa'))
+    o = _options(os.path.join(DATA, 'backbone.nwk'), os.path.join(DATA, 'ref.fa'), exe)
     assert R.reestimate_backbone(o) is True
     before = R.from_newick(open(os.path.join(DATA, 'backbone.nwk')).read())
     after = R.from_newick(open(o.tree_fp).read())
@@ -153,15 +176,14 @@ def test_wrapper_with_the_bundled_fasttree_on_the_example_data():
     assert t.n_leaves == 490
 
 
-@pytest.mark.skipif(not os.path.exists(BUNDLED), reason='the reference tree (with its bundled FastTree) is only in the build container')
-def test_bundled_fasttree_on_a_rooted_tree_keeps_the_root_edge(tmp_path):
+def test_bundled_fasttree_on_a_rooted_tree_keeps_the_root_edge(tmp_path, golden_dir):
     d = synth.make_dataset(60, 400, 1)
     tree_fp, ref_fp = tmp_path / 'bb.nwk', tmp_path / 'ref.fa'
     open(tree_fp, 'w').write(d.newick + '\n')
     with open(ref_fp, 'w') as f:
         for n, s in zip(d.ref_names, d.ref_seqs):
             f.write('>%s\n%s\n' % (n, s.tobytes().decode()))
-    o = _options(str(tree_fp), str(ref_fp), BUNDLED)
+    o = _options(str(tree_fp), str(ref_fp), _bundled_fasttree(tmp_path, os.path.join(golden_dir, 'g9_fasttree_rooted60.nwk'), ref_fp))
     assert R.reestimate_backbone(o) is True
     before, after = R.from_newick(d.newick), R.from_newick(open(o.tree_fp).read())
     assert len(after.children) == 2
