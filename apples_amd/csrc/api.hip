@@ -700,7 +700,9 @@ int setup_alignment(apples_ctx *ctx, const apples_tree *t, const apples_alignmen
         }
         dev_free(d_exotic);
         // pre-expanded reference image for the GEMM form of the fused pass (dist_gemm.hip): 2 bytes per site
-        if (a.all_singleton && a.planes == 2 && a.L <= GEMM_MAX_L && dist_mfma_enabled(ctx) && !(ctx->dbg & APPLES_DBG_NO_DIST_GEMM)) {
+        // (alignments of GEMM_LONG_MIN_L sites and more: the same image, read by k_jc69_gemm_long)
+        if (a.all_singleton && a.planes == 2 && (a.L <= GEMM_MAX_L || a.L >= GEMM_LONG_MIN_L) && dist_mfma_enabled(ctx) &&
+            !(ctx->dbg & APPLES_DBG_NO_DIST_GEMM)) {
             // (the image's own allocation marks the context's fp4 images as compact: 64 bytes per 64-site block)
             if (dev_alloc(ctx, &a.ref_f4, a.slots_pad * (int64_t)a.G * 128)) return 1;
             if (launch_expand_queries_f4(ctx, a.raw, a.n_rows, a.ref_f4, a.slots_pad, ctx->stream, a.d_slot_row)) return 1;
@@ -2165,6 +2167,33 @@ static GemmThreshold gemm_threshold(const std::vector<int32_t> &mmax, double f) 
     return g;
 }
 
+// The K-split pass's integer screen (k_jc69_gemm_long; apples_ctx::jc_bound_long): per valid count -1 where the overlap rule
+// excludes it, else min(valid, m* + 1), m* = the largest mismatch count whose distance -- dist.hip's jc69_from_counts with the
+// host's log -- passes 0 <= d <= f, found by bisection (d grows with mism until 1 - 4 p / 3 reaches 0, then it is -1).  The
+// "+ 1" makes the screen a superset of the rule whatever the last bit of the host's log: the kernel's exact test decides.
+// 65 536 entries whatever L (the kernel indexes with a 16-bit count).
+static std::vector<int32_t> jc_bound_long_table(int L, double overlap, double f) {
+    std::vector<int32_t> bound(65536, -1);
+    auto passes = [&](int m, int v) {
+        const double p = (double)m * 1.0 / (double)v;
+        if (p - 2.220446049250313e-16 < 0) return 0.0 <= f;
+        const double loc = 1 - (4 * p / 3);
+        if (0 >= loc) return false;
+        const double d = -0.75 * std::log(loc);
+        return d >= 0 && d <= f;
+    };
+    for (int v = 1; v <= L; ++v) {
+        if ((double)v / (double)L < overlap) continue;
+        int lo = -1, hi = v + 1;  // passes below lo + 1, not from hi on
+        while (hi - lo > 1) {
+            const int mid = lo + (hi - lo) / 2;
+            if (passes(mid, v)) lo = mid; else hi = mid;
+        }
+        bound[v] = std::min(v, lo + 1);
+    }
+    return bound;
+}
+
 int apples_set_params(apples_ctx *ctx, const apples_params *params) {
     HIP_TRY(ctx, hipSetDevice(ctx->device));  // the caller's thread may have another device current
     int model = ctx->params.model;
@@ -2173,6 +2202,7 @@ int apples_set_params(apples_ctx *ctx, const apples_params *params) {
     ctx->params.debug = ctx->dbg;  // (the switches are fixed at creation)
     ctx->params.knobs = nullptr;   // (so are the knobs: read once, apples_ctx_create)
     ctx->params.jc_lut = nullptr;
+    std::vector<int32_t> bound_long;  // the K-split pass's screen where the caller tabulates the distances: from the table itself
     if (params->jc_lut && params->jc_lut_len > 0) {
         int64_t L = ctx->has_aln ? ctx->aln.L : 0;
         int64_t need = (L + 1) * (L + 2) / 2;
@@ -2196,6 +2226,8 @@ int apples_set_params(apples_ctx *ctx, const apples_params *params) {
                     if (!(row[m] >= 0 && row[m] <= params->filt_threshold)) monotone = false;
                 mmax[v] = last;
             }
+            // (the last mismatch count that passes, monotone table or not: nothing beyond it survives the kernel's exact test)
+            if (L >= GEMM_LONG_MIN_L) { bound_long.assign(65536, -1); std::copy(mmax.begin(), mmax.end(), bound_long.begin()); }
             dev_free(ctx->jc_mmax_true);
             ctx->jc_mmax_true = nullptr;
             if (monotone && ctx->aln.ex_max > 0) {
@@ -2224,6 +2256,15 @@ int apples_set_params(apples_ctx *ctx, const apples_params *params) {
         dev_free(ctx->jc_mmax);
         ctx->jc_mmax = nullptr;
         ctx->gemm_thr = GemmThreshold();
+    }
+    // alignments beyond the 13-bit packed survivor word: the K-split pass's screen at the present -f / -V
+    dev_free(ctx->jc_bound_long);
+    ctx->jc_bound_long = nullptr;
+    if (ctx->has_aln && ctx->params.model == APPLES_JC69 && ctx->aln.ref_f4 && ctx->aln.L >= GEMM_LONG_MIN_L) {
+        const std::vector<int32_t> bound = !bound_long.empty() ? bound_long
+                                           : jc_bound_long_table(ctx->aln.L, params->overlap_frac, params->filt_threshold);
+        if (dev_upload(ctx, &ctx->jc_bound_long, bound.data(), (int64_t)bound.size())) return 1;
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     }
     return 0;
 }
@@ -2271,7 +2312,7 @@ void apples_ctx_destroy(apples_ctx *ctx) {
     DevAlign &a = ctx->aln;
     dev_free(a.raw); dev_free(a.d_slot_row); dev_free(a.packed); dev_free(a.ref_f4); dev_free(a.rep_boff); dev_free(a.rep_loff); dev_free(a.loose_mp); dev_free(a.blk_rec_i); dev_free(a.blk_rec_e); dev_free(a.blk_rec_c); dev_free(a.blk_rec_p); dev_free(a.blk_pk_i); dev_free(a.blk_pk_e); dev_free(a.blk_stat[0]); dev_free(a.blk_stat[1]); dev_free(a.rep_soff); dev_free(a.cl_order); dev_free(a.mem_block); dev_free(a.blk_root); dev_free(a.blk_rslot); dev_free(a.blk_nodes); dev_free(a.e_of_slot); dev_free(a.e_of_blk); dev_free(a.e_node); dev_free(a.lvl_e); dev_free(a.rep_packed); dev_free(a.packed_rm); dev_free(a.aa_rep_idx); dev_free(a.aa_rep_mask); dev_free(a.aa_cm_idx); dev_free(a.aa_cm_mask); dev_free(a.aa_idx); dev_free(a.aa_mask); dev_free(a.sd_ref4); dev_free(a.sd_nvr); dev_free(a.aa_rows); dev_free(a.aa_mrows); dev_free(ctx->sd_tq4); dev_free(ctx->sd_list_img); dev_free(ctx->sd_list_ints); dev_free(a.slot_node); dev_free(a.slot_level); dev_free(a.lvl_slots);
     dev_free(a.slot_rep); dev_free(a.slot_mpos); dev_free(a.rep_slot); dev_free(a.rep_moff); dev_free(a.mem_slot);
-    dev_free(ctx->jc_lut); dev_free(ctx->jc_mmax); dev_free(ctx->jc_mmax_true); dev_free(ctx->blosum); dev_free(ctx->d_col_perm); dev_free(ctx->d_col_node);
+    dev_free(ctx->jc_lut); dev_free(ctx->jc_mmax); dev_free(ctx->jc_mmax_true); dev_free(ctx->jc_bound_long); dev_free(ctx->blosum); dev_free(ctx->d_col_perm); dev_free(ctx->d_col_node);
     dev_free(ctx->d_col_level);
     for (int i = 0; i < 8; ++i)
         if (ctx->ev[i]) (void)hipEventDestroy(ctx->ev[i]);
@@ -2852,7 +2893,7 @@ const char *apples_describe(apples_ctx *ctx) {
              "{\"device\": \"%s\", \"compute_units\": %d, \"n_nodes\": %d, \"height\": %d, \"max_children\": %d, \"n_rows\": %lld, "
              "\"n_refs\": %lld, \"n_reps\": %lld, \"length\": %d, \"code_planes\": %d, \"all_singleton\": %d, "
              "\"packed_bytes\": %lld, \"batch\": %lld, \"sweep_workgroups\": %d, \"sweep_team_cap\": %lld, \"sweep_big_workgroups\": %d, \"jc_lut\": %d, \"sweep\": \"%s\", "
-             "\"fused_distance_pass\": \"%s\", \"fp4_reference_image_bytes\": %lld, \"sweep_layout\": \"%s\", \"cluster_fused\": %d, "
+             "\"fused_distance_pass\": \"%s\", \"gemm_split_sites\": %d, \"k_split_launches\": %lld, \"fp4_reference_image_bytes\": %lld, \"sweep_layout\": \"%s\", \"cluster_fused\": %d, "
              "\"scoredist_filter\": %d, \"scoredist_image_bytes\": %lld, \"cluster_blocks\": %d, \"block_items_last_batch\": %d, \"block_tiles_last_batch\": %d, "
              "\"exotic_symbols_as_gaps\": %d, \"exotic_sites_max_per_row\": %d, \"eight_plane_copy\": %d, "
              "\"ragged_rows\": %d, \"row_small\": %lld, \"big_rows\": %lld, \"big_rows_last_batch\": %d, \"full_rows_for_good\": %d}",
@@ -2861,8 +2902,11 @@ const char *apples_describe(apples_ctx *ctx) {
              (long long)((int64_t)a.G * (a.planes + 1) * a.slots_pad * 16), (long long)ctx->ws.batch, ctx->ws.small.wgs,
              (long long)ctx->ws.small.cap, ctx->ws.big.wgs, ctx->jc_lut ? 1 : 0, ctx->tree.scan ? "scan" : "levels",
              // which kernel the fused pass of ACGT- query blocks runs on (dist_gemm.hip / dist.hip k_jc69_mfma / k_jc69 or k_scoredist)
+             // (from GEMM_LONG_MIN_L sites on the packed survivor word no longer holds the counts: the K-split GEMM, or the bit-plane kernel)
              dist_gemm_usable(ctx) ? (ctx->gemm_thr.ok ? "fp4 gemm, linear threshold" : "fp4 gemm, threshold table")
-                                   : (a.planes == 2 && dist_mfma_enabled(ctx) ? "fp4 mfma, bit-plane fed" : "valu"),
+             : dist_gemm_long_usable(ctx) ? "fp4 gemm, k-split"
+             : (a.planes == 2 && dist_mfma_enabled(ctx) && a.L < GEMM_LONG_MIN_L ? "fp4 mfma, bit-plane fed" : "valu"),
+             dist_gemm_long_usable(ctx) ? GEMM_SPLIT_STEPS * 64 : 0, (long long)ctx->gemm_long_launches,
              (long long)(a.ref_f4 ? a.slots_pad * (int64_t)a.G * 128 : 0),
              // how the level-loop sweep knows a query's subtree: merged level lists / node bits in LDS / tagged node map
              // (lean: sweep_lean.hip on big binary trees -- the workspace decides; before there is one, what a plain MLSE / ME pass will get)

@@ -114,6 +114,10 @@ struct GemmThreshold {
 };
 #define GEMM_MAX_L13 2046  // the merged accumulator with the validity sum at 2^13 decodes exactly while valid <= 2046 ...
 #define GEMM_MAX_L 4092    // ... and at 2^12, by the congruence of dist_gemm.hip's header, while valid <= 4092
+// Longer alignments (dist_gemm.hip: k_jc69_gemm_long): the 2^12 form in splits of the K loop, each decoded into integer totals in registers
+#define GEMM_LONG_MIN_L 8192    // alignments from this length on take the K-split kernel (singleton ACGT- contexts)
+#define GEMM_SPLIT_STEPS 60     // 64-site steps per split: 3 840 sites, a multiple of the three LDS generations; the last split -- up to 57
+                                // steps of remainder and 4 of the tail -- stays within GEMM_MAX_L as well
 
 struct DevAlign {
     int64_t n_rows = 0, n_refs = 0, n_reps = 0;
@@ -332,6 +336,12 @@ struct apples_ctx {
     int32_t *jc_mmax = nullptr;  // [L+1] largest mismatch count with 0 <= lut <= threshold, per valid count
     int32_t *jc_mmax_true = nullptr;  // jc_mmax is the FILTER's table where the reference holds bytes beyond ACGT- (a pair's counts may still
                                       // grow by up to ex_max: set_params); this is the rule itself, what k_exotic_fix tests.  nullptr: jc_mmax is
+    int32_t *jc_bound_long = nullptr;  // [65 536] (the kernel indexes with a 16-bit count; -1 beyond L) the K-split pass's integer screen, a
+                                       // superset of the rule.  Without a distance table: -1 where the overlap rule excludes the valid
+                                       // count, else min(valid, m* + 1), m* = the largest mismatch count the host's log lets pass
+                                       // (api.hip: jc_bound_long_table).  With one: the largest mismatch count whose TABULATED distance
+                                       // passes.  The kernel's own exact test decides.  NOT jc_mmax: that one switches k_jc69 onto the table
+    int64_t gemm_long_launches = 0;    // launches of k_jc69_gemm_long so far (describe(): "k_split_launches")
     double *blosum = nullptr;  // 21x21 table (row/col 20 = gap -> 0)
     uint8_t *sd_tq4 = nullptr; // [20][20] fp4 codes of the table rounded down to the grid {0, .5, 1, 1.5, 2, 3, 4, 6} / 4 (dist_sd.hip)
     Workspace ws;
@@ -558,6 +568,10 @@ int launch_expand_queries_f4(apples_ctx *ctx, const uint8_t *d_raw, int64_t n, u
 // dist_gemm.hip
 bool dist_gemm_usable(const apples_ctx *ctx);
 int launch_counts_gemm(apples_ctx *ctx, const QueryBlock &qb, int64_t q0, int64_t nq, int32_t *seg_slot, int32_t *seg_cnt);
+// k_jc69_gemm_long: the fused pass of 2-plane blocks on alignments of GEMM_LONG_MIN_L sites and more; writes k_jc69 MODE 1's format
+bool dist_gemm_long_usable(const apples_ctx *ctx);
+int launch_counts_gemm_long(apples_ctx *ctx, const QueryBlock &qb, int64_t q0, int64_t nq, double *seg_d, int32_t *seg_slot,
+                            int32_t *seg_cnt);
 int launch_counts_fused(apples_ctx *ctx, const QueryBlock &qb, int64_t q0, int64_t nq, int tile, double *seg_d,
                         int32_t *seg_slot, int32_t *seg_cnt);
 int launch_counts_listed(apples_ctx *ctx, const QueryBlock &qb, int64_t q0, int64_t nq_max, const int32_t *qlist,

@@ -14,18 +14,6 @@
 #include "common.h"
 #include "libm_log.h"
 
-__device__ __forceinline__ double jc69_from_counts(uint32_t mism, uint32_t valid, int L, double overlap,
-                                                   const double *__restrict__ lut) {
-    if (lut) return lut[(int64_t)valid * (valid + 1) / 2 + mism];
-    // apples/distance.py:735-745, literal order
-    if (valid == 0 || (double)valid / (double)L < overlap) return -1.0;
-    double p = (double)mism * 1.0 / (double)valid;
-    if (p - 2.220446049250313e-16 < 0) return 0.0;
-    double loc = 1 - (4 * p / 3);
-    if (0 >= loc) return -1.0;
-    return -0.75 * log_libm(loc);
-}
-
 // popcount with the instruction's own accumulate operand (D = popc(S0) + S1); hipcc otherwise emits
 // v_bcnt ..., 0 followed by separate adds
 __device__ __forceinline__ uint32_t bcnt_acc(uint32_t x, uint32_t acc) {
@@ -639,6 +627,9 @@ int launch_counts_fused(apples_ctx *ctx, const QueryBlock &qb, int64_t q0, int64
     if (fused_counts_format(ctx, qb))
         return dist_gemm_usable(ctx) ? launch_counts_gemm(ctx, qb, q0, nq, seg_slot, seg_cnt)
                                      : launch_mfma<1>(ctx, qb, q0, nq, seg_d, nullptr, seg_slot, seg_cnt);
+    // alignments of GEMM_LONG_MIN_L sites and more, ACGT- blocks: the K-split GEMM writes the format of k_jc69 MODE 1
+    if (dist_gemm_long_usable(ctx) && qb.qf4 && qb.planes == 2 && !exact8_rows(ctx, qb))
+        return launch_counts_gemm_long(ctx, qb, q0, nq, seg_d, seg_slot, seg_cnt);
     if (!exact8_rows(ctx, qb)) launch_jc69_tile<2, 1>(ctx, qb, q0, nq, tile, seg_d, nullptr, seg_slot, seg_cnt, nullptr, nullptr);
     else launch_jc69_tile<8, 1>(ctx, qb, q0, nq, tile, seg_d, nullptr, seg_slot, seg_cnt, nullptr, nullptr);
     HIP_TRY(ctx, hipGetLastError());

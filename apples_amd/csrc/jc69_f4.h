@@ -32,3 +32,19 @@ __device__ __forceinline__ v16f_t mfma_f4(const v4i_t &a, const v4i_t &b, const 
     return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a8, b8, c, 4, 4, 0, 0, 0, 0);
 }
 
+// ... with the first operand scaled by 2^VS (E8M0 scales: 127 + VS on the first operand, 127 = 1.0 on the second): how
+// dist_gemm.hip's kernels carry the validity sum in the accumulator of the t.t sums
+template <int VS>
+__device__ __forceinline__ v16f_t mfma_f4_v(const v4i_t &a, const v4i_t &b, const v16f_t &c) {
+    const v8i_t a8 = {a[0], a[1], a[2], a[3], 0, 0, 0, 0}, b8 = {b[0], b[1], b[2], b[3], 0, 0, 0, 0};
+    return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a8, b8, c, 4, 4, 0, 127 + VS, 0, 127);
+}
+
+// acc -> (valid, 4 mism) of the VS = 12 form (dist_gemm.hip's header): valid = the count in [acc / 4099, acc / 4095] with valid = 3 acc (mod 4)
+__device__ __forceinline__ void decode12(float S, int &valid, int &mism4) {
+    const int A = (int)S;
+    int v = (A + 4098) / 4099;
+    v += (3 * A - v) & 3;
+    valid = v;
+    mism4 = 4099 * v - A;
+}

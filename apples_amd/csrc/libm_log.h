@@ -66,3 +66,16 @@ __device__ __forceinline__ double log_libm(double x) {
     const double y = fma(r3, p, lo);
     return y + hi;
 }
+
+// the JC69 distance of a pair from its counts (lut: the host's table of the same expression, [valid (valid + 1) / 2 + mism])
+__device__ __forceinline__ double jc69_from_counts(uint32_t mism, uint32_t valid, int L, double overlap,
+                                                   const double *__restrict__ lut) {
+    if (lut) return lut[(int64_t)valid * (valid + 1) / 2 + mism];
+    // apples/distance.py:735-745, literal order
+    if (valid == 0 || (double)valid / (double)L < overlap) return -1.0;
+    double p = (double)mism * 1.0 / (double)valid;
+    if (p - 2.220446049250313e-16 < 0) return 0.0;
+    double loc = 1 - (4 * p / 3);
+    if (0 >= loc) return -1.0;
+    return -0.75 * log_libm(loc);
+}
