@@ -709,9 +709,26 @@ int setup_alignment(apples_ctx *ctx, const apples_tree *t, const apples_alignmen
             HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         }
         // clustered reference on the ACGT- fast path: panels for the fused selection by representatives
-        if (!a.all_singleton && a.planes == 2 && a.n_refs <= SELECT_CLUSTERS_MAX_SLOTS && a.G <= 64 &&
-            !(ctx->dbg & APPLES_DBG_NO_FUSE) && dist_mfma_enabled(ctx))
+        // (beyond 64 word groups -- 8 192 sites -- the route is the long one: the representatives' pass on k_jc69_gemm_long, which
+        // APPLES_DBG_NO_DIST_GEMM turns off; 8 192 sites exactly build the panels either way, as they always did)
+        const bool cl_long = a.L >= GEMM_LONG_MIN_L && !(ctx->dbg & APPLES_DBG_NO_DIST_GEMM);
+        if (!a.all_singleton && a.planes == 2 && a.n_refs <= SELECT_CLUSTERS_MAX_SLOTS && (a.G <= 64 || cl_long) &&
+            !(ctx->dbg & APPLES_DBG_NO_FUSE) && dist_mfma_enabled(ctx)) {
             if (launch_build_cluster_panels(ctx)) return 1;
+            if (cl_long) {
+                // the representatives' rows once more as a compact fp4 image in representative order (k_jc69_gemm_long's reference
+                // operand: reps_pad is a multiple of its 256-row tiles, the padding rows are all-gap), through a row map
+                // (a.raw holds the caller's rows in the caller's order: the map is the caller's rep_row)
+                int32_t *d_rep_row = nullptr;
+                if (dev_upload(ctx, &d_rep_row, al->rep_row, a.n_reps)) return 1;
+                // (rep_f4's allocation makes the context's images compact)
+                int bad = dev_alloc(ctx, &a.rep_f4, a.reps_pad * (int64_t)a.G * 128) ||
+                          launch_expand_queries_f4(ctx, a.raw, a.n_reps, a.rep_f4, a.reps_pad, ctx->stream, d_rep_row);
+                if (!bad && hipStreamSynchronize(ctx->stream) != hipSuccess) { ctx->err = "representative image: stream synchronize failed"; bad = 1; }
+                dev_free(d_rep_row);
+                if (bad) return 1;
+            }
+        }
     }
     return 0;
 }
@@ -742,9 +759,9 @@ int repack_to_bytes(apples_ctx *ctx) {  // a query block carries symbols beyond 
     if (a.planes == 8) return 0;
     int *d_exotic = nullptr;
     if (dev_alloc(ctx, &d_exotic, 1)) return 1;
-    dev_free(a.rep_packed); dev_free(a.packed_rm); dev_free(a.ref_f4);  // the fast paths are for ACGT- contexts only
+    dev_free(a.rep_packed); dev_free(a.packed_rm); dev_free(a.ref_f4); dev_free(a.rep_f4);  // the fast paths are for ACGT- contexts only
     a.rep_packed = a.packed_rm = nullptr;
-    a.ref_f4 = nullptr;
+    a.ref_f4 = a.rep_f4 = nullptr;
     dev_free(a.packed);
     a.planes = 8;
     int64_t words = (int64_t)a.G * 9 * a.slots_pad;
@@ -1166,7 +1183,7 @@ int fill_block(apples_ctx *ctx, QueryBlock *qb, const uint8_t *queries, int64_t 
     if (qb->qf4) {
         const int64_t n128 = round_up(qb->n_pad, 256) + 256;
         const bool last = q0 + nq >= qb->n;  // the last chunk also zeroes the image's padding rows
-        if (a.ref_f4) {  // compact, tiled images beside a reference image: addressed by image row
+        if (f4_images_compact(ctx)) {  // compact, tiled images beside a reference or representative image: addressed by image row
             if (launch_expand_queries_f4(ctx, qb->raw + q0 * a.L, nq, qb->qf4, last ? n128 - q0 : nq, st, nullptr, q0)) return 1;
         } else if (launch_expand_queries_f4(ctx, qb->raw + q0 * a.L, nq, qb->qf4 + q0 * (int64_t)a.G * 256, last ? n128 - q0 : nq, st)) return 1;
     }
@@ -1540,8 +1557,13 @@ int run_block_main(apples_ctx *ctx, QueryBlock &qb, const Feeder *feed) {
     // (scoredist contexts, csd: full rows of the distances to the representatives in place of the matrix-core pass, k_cluster_dist_sd
     // for the members)
     const bool csd = !no_fuse && !a.all_singleton && ctx->params.model == APPLES_SCOREDIST && a.aa_rep_idx;
-    const bool cfused = csd || (!no_fuse && !a.all_singleton && ctx->params.model == APPLES_JC69 && a.rep_packed && a.packed_rm &&
-                                fused_counts_format(ctx, qb));
+    // (alignments of GEMM_LONG_MIN_L sites and more, cl_long: the representatives' pass is the K-split GEMM over their fp4 image, the
+    // selection and member-distance kernels run in their long forms -- fp64 distances from jc69_from_counts, no 13-bit packed counts)
+    const bool cl_long = !no_fuse && !a.all_singleton && ctx->params.model == APPLES_JC69 && a.planes == 2 && a.rep_packed && a.packed_rm &&
+                         a.rep_f4 && ctx->jc_bound_long && a.L >= GEMM_LONG_MIN_L && qb.planes == 2 && qb.qf4 && !qb.exact8 &&
+                         !(ctx->dbg & APPLES_DBG_NO_DIST_GEMM);
+    const bool cfused = csd || cl_long || (!no_fuse && !a.all_singleton && ctx->params.model == APPLES_JC69 && a.rep_packed && a.packed_rm &&
+                                           fused_counts_format(ctx, qb));
     // scoredist with singleton clusters: threshold compaction in the distance kernel's epilogue as well
     const bool sfused = !no_fuse && a.all_singleton && ctx->params.model == APPLES_SCOREDIST;
     const bool fused = !no_fuse && (((a.all_singleton || cfused) && ctx->params.model == APPLES_JC69) || sfused || csd);
@@ -1697,13 +1719,15 @@ int run_block_main(apples_ctx *ctx, QueryBlock &qb, const Feeder *feed) {
         };
         if (cfused) {
             HIP_TRY(ctx, hipEventRecord(e[0], front));
-            if (csd) {
+            if (csd || cl_long) {  // (both keep fp64 distances to the representatives beside the survivor lists)
                 if (ctx->sd_rep_d_cap < w.batch * a.reps_pad) {
                     dev_free(ctx->sd_rep_d); ctx->sd_rep_d = nullptr; ctx->sd_rep_d_cap = 0;
                     if (dev_alloc(ctx, &ctx->sd_rep_d, w.batch * a.reps_pad)) return 1;
                     ctx->sd_rep_d_cap = w.batch * a.reps_pad;
                 }
-                if (launch_scoredist_reps(ctx, qb, q0, nq, ctx->sd_rep_d, w.seg_slot, w.seg_cnt)) return 1;  // (writes every segment's count)
+                // (both write every segment's count)
+                if (csd ? launch_scoredist_reps(ctx, qb, q0, nq, ctx->sd_rep_d, w.seg_slot, w.seg_cnt)
+                        : launch_counts_gemm_long(ctx, qb, q0, nq, ctx->sd_rep_d, w.seg_slot, w.seg_cnt, a.rep_f4, a.reps_pad)) return 1;
             } else {
                 HIP_TRY(ctx, hipMemsetAsync(w.seg_cnt, 0, (size_t)nq * (a.reps_pad / 64) * sizeof(int32_t), front));
                 if (launch_counts_reps(ctx, qb, q0, nq, w.seg_slot, w.seg_cnt)) return 1;
@@ -1712,6 +1736,7 @@ int run_block_main(apples_ctx *ctx, QueryBlock &qb, const Feeder *feed) {
             ++launches;
             SelectArgs sa = select_args_alignment(ctx, qb, q0);
             sa.seg_lut = ctx->jc_lut;
+            if (cl_long) { sa.cl_long = 1; sa.rep_seg_d = ctx->sd_rep_d; }  // (seg_lut: the caller's table at 8 192 sites, nullptr beyond)
             if (csd) {
                 const int Lpad = (a.L + 15) / 16 * 16;
                 sa.seg_lut = nullptr; sa.rep_dist = ctx->sd_rep_d;
@@ -2260,11 +2285,17 @@ int apples_set_params(apples_ctx *ctx, const apples_params *params) {
     // alignments beyond the 13-bit packed survivor word: the K-split pass's screen at the present -f / -V
     dev_free(ctx->jc_bound_long);
     ctx->jc_bound_long = nullptr;
-    if (ctx->has_aln && ctx->params.model == APPLES_JC69 && ctx->aln.ref_f4 && ctx->aln.L >= GEMM_LONG_MIN_L) {
+    // (for the reference image of a singleton context or the representatives' image of a clustered one.  The representatives'
+    // image has all-gap padding rows, valid = 0: entry 0 must keep them out.  It is -1 from the bisection, which starts at valid = 1,
+    // and from every table whose entry for no valid site does not pass; a clustered context whose table lets it pass gets no screen
+    // and so stays on the general route)
+    if (ctx->has_aln && ctx->params.model == APPLES_JC69 && (ctx->aln.ref_f4 || ctx->aln.rep_f4) && ctx->aln.L >= GEMM_LONG_MIN_L) {
         const std::vector<int32_t> bound = !bound_long.empty() ? bound_long
                                            : jc_bound_long_table(ctx->aln.L, params->overlap_frac, params->filt_threshold);
-        if (dev_upload(ctx, &ctx->jc_bound_long, bound.data(), (int64_t)bound.size())) return 1;
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        if (ctx->aln.ref_f4 || bound[0] < 0) {
+            if (dev_upload(ctx, &ctx->jc_bound_long, bound.data(), (int64_t)bound.size())) return 1;
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        }
     }
     return 0;
 }
@@ -2310,7 +2341,7 @@ void apples_ctx_destroy(apples_ctx *ctx) {
     DevTree &t = ctx->tree;
     dev_free(t.parent); dev_free(t.edge_len); dev_free(t.child_off); dev_free(t.child_idx); dev_free(t.level); dev_free(t.rec); dev_free(t.lvlw); dev_free(t.lnode); dev_free(t.rec_l); dev_free(t.npos); dev_free(t.pe); dev_free(t.leaf_info); dev_free(t.anc); dev_free(t.rmq);
     DevAlign &a = ctx->aln;
-    dev_free(a.raw); dev_free(a.d_slot_row); dev_free(a.packed); dev_free(a.ref_f4); dev_free(a.rep_boff); dev_free(a.rep_loff); dev_free(a.loose_mp); dev_free(a.blk_rec_i); dev_free(a.blk_rec_e); dev_free(a.blk_rec_c); dev_free(a.blk_rec_p); dev_free(a.blk_pk_i); dev_free(a.blk_pk_e); dev_free(a.blk_stat[0]); dev_free(a.blk_stat[1]); dev_free(a.rep_soff); dev_free(a.cl_order); dev_free(a.mem_block); dev_free(a.blk_root); dev_free(a.blk_rslot); dev_free(a.blk_nodes); dev_free(a.e_of_slot); dev_free(a.e_of_blk); dev_free(a.e_node); dev_free(a.lvl_e); dev_free(a.rep_packed); dev_free(a.packed_rm); dev_free(a.aa_rep_idx); dev_free(a.aa_rep_mask); dev_free(a.aa_cm_idx); dev_free(a.aa_cm_mask); dev_free(a.aa_idx); dev_free(a.aa_mask); dev_free(a.sd_ref4); dev_free(a.sd_nvr); dev_free(a.aa_rows); dev_free(a.aa_mrows); dev_free(ctx->sd_tq4); dev_free(ctx->sd_list_img); dev_free(ctx->sd_list_ints); dev_free(a.slot_node); dev_free(a.slot_level); dev_free(a.lvl_slots);
+    dev_free(a.raw); dev_free(a.d_slot_row); dev_free(a.packed); dev_free(a.ref_f4); dev_free(a.rep_f4); dev_free(a.rep_boff); dev_free(a.rep_loff); dev_free(a.loose_mp); dev_free(a.blk_rec_i); dev_free(a.blk_rec_e); dev_free(a.blk_rec_c); dev_free(a.blk_rec_p); dev_free(a.blk_pk_i); dev_free(a.blk_pk_e); dev_free(a.blk_stat[0]); dev_free(a.blk_stat[1]); dev_free(a.rep_soff); dev_free(a.cl_order); dev_free(a.mem_block); dev_free(a.blk_root); dev_free(a.blk_rslot); dev_free(a.blk_nodes); dev_free(a.e_of_slot); dev_free(a.e_of_blk); dev_free(a.e_node); dev_free(a.lvl_e); dev_free(a.rep_packed); dev_free(a.packed_rm); dev_free(a.aa_rep_idx); dev_free(a.aa_rep_mask); dev_free(a.aa_cm_idx); dev_free(a.aa_cm_mask); dev_free(a.aa_idx); dev_free(a.aa_mask); dev_free(a.sd_ref4); dev_free(a.sd_nvr); dev_free(a.aa_rows); dev_free(a.aa_mrows); dev_free(ctx->sd_tq4); dev_free(ctx->sd_list_img); dev_free(ctx->sd_list_ints); dev_free(a.slot_node); dev_free(a.slot_level); dev_free(a.lvl_slots);
     dev_free(a.slot_rep); dev_free(a.slot_mpos); dev_free(a.rep_slot); dev_free(a.rep_moff); dev_free(a.mem_slot);
     dev_free(ctx->jc_lut); dev_free(ctx->jc_mmax); dev_free(ctx->jc_mmax_true); dev_free(ctx->jc_bound_long); dev_free(ctx->blosum); dev_free(ctx->d_col_perm); dev_free(ctx->d_col_node);
     dev_free(ctx->d_col_level);
@@ -2893,7 +2924,7 @@ const char *apples_describe(apples_ctx *ctx) {
              "{\"device\": \"%s\", \"compute_units\": %d, \"n_nodes\": %d, \"height\": %d, \"max_children\": %d, \"n_rows\": %lld, "
              "\"n_refs\": %lld, \"n_reps\": %lld, \"length\": %d, \"code_planes\": %d, \"all_singleton\": %d, "
              "\"packed_bytes\": %lld, \"batch\": %lld, \"sweep_workgroups\": %d, \"sweep_team_cap\": %lld, \"sweep_big_workgroups\": %d, \"jc_lut\": %d, \"sweep\": \"%s\", "
-             "\"fused_distance_pass\": \"%s\", \"gemm_split_sites\": %d, \"k_split_launches\": %lld, \"fp4_reference_image_bytes\": %lld, \"sweep_layout\": \"%s\", \"cluster_fused\": %d, "
+             "\"fused_distance_pass\": \"%s\", \"gemm_split_sites\": %d, \"k_split_launches\": %lld, \"cluster_k_split_launches\": %lld, \"fp4_reference_image_bytes\": %lld, \"sweep_layout\": \"%s\", \"cluster_fused\": %d, "
              "\"scoredist_filter\": %d, \"scoredist_image_bytes\": %lld, \"cluster_blocks\": %d, \"block_items_last_batch\": %d, \"block_tiles_last_batch\": %d, "
              "\"exotic_symbols_as_gaps\": %d, \"exotic_sites_max_per_row\": %d, \"eight_plane_copy\": %d, "
              "\"ragged_rows\": %d, \"row_small\": %lld, \"big_rows\": %lld, \"big_rows_last_batch\": %d, \"full_rows_for_good\": %d}",
@@ -2905,8 +2936,11 @@ const char *apples_describe(apples_ctx *ctx) {
              // (from GEMM_LONG_MIN_L sites on the packed survivor word no longer holds the counts: the K-split GEMM, or the bit-plane kernel)
              dist_gemm_usable(ctx) ? (ctx->gemm_thr.ok ? "fp4 gemm, linear threshold" : "fp4 gemm, threshold table")
              : dist_gemm_long_usable(ctx) ? "fp4 gemm, k-split"
+             // (a clustered context of these lengths: the same kernel over the representatives' image, the fused selection behind it)
+             : (a.rep_f4 && ctx->jc_bound_long && !(ctx->dbg & (APPLES_DBG_NO_DIST_GEMM | APPLES_DBG_NO_FUSE))) ? "fp4 gemm, k-split over representatives"
              : (a.planes == 2 && dist_mfma_enabled(ctx) && a.L < GEMM_LONG_MIN_L ? "fp4 mfma, bit-plane fed" : "valu"),
              dist_gemm_long_usable(ctx) ? GEMM_SPLIT_STEPS * 64 : 0, (long long)ctx->gemm_long_launches,
+             (long long)ctx->cluster_long_launches,  // ... of the same kernel over the representatives' image (clustered contexts of 8 192+ sites)
              (long long)(a.ref_f4 ? a.slots_pad * (int64_t)a.G * 128 : 0),
              // how the level-loop sweep knows a query's subtree: merged level lists / node bits in LDS / tagged node map
              // (lean: sweep_lean.hip on big binary trees -- the workspace decides; before there is one, what a plain MLSE / ME pass will get)

@@ -144,6 +144,8 @@ struct DevAlign {
     uint4 *packed_rm = nullptr;   // the member rows cluster by cluster, interleaved per plane word (dist.hip:k_cluster_major): [n_refs * G*3]
     uint4 *rep_packed = nullptr;  // [G][3][reps_pad] the representatives' rows, in representative order
     int64_t reps_pad = 0;
+    uint8_t *rep_f4 = nullptr;    // alignments of GEMM_LONG_MIN_L sites and more: the representatives' rows in representative order as a compact fp4
+                                  // operand image ([reps_pad][2G] blocks in ref_f4's tiled form; padding rows all-gap) -- k_jc69_gemm_long reads it
     // ... and of scoredist contexts (the default route of -p): the representatives' rows in representative order, in the layout
     // of aa_idx / aa_mask with reps_pad in place of slots_pad (what k_scoredist runs over in place of every slot)
     uint8_t *aa_rep_idx = nullptr;   // [Lpad16/16][reps_pad][16]
@@ -218,7 +220,7 @@ struct QueryBlock {
     QueryBlock *ex_block = nullptr;  // the block's few queries with such bytes once more as an exact8 block of their own ...
     int32_t *ex_idx = nullptr;       // ... and which queries they are [ex_block->n] (run_block places them last and copies the structs over)
     uint8_t *qf4 = nullptr;       // fp4 operand image for the matrix-core distance kernels: [n_pad128][2G][4][32 B] (t1, t2, t3, v) for
-                                  // k_jc69_mfma; beside a reference image (DevAlign::ref_f4) the compact tiled form of dist_gemm.hip
+                                  // k_jc69_mfma; beside a reference or representative image (DevAlign::ref_f4 / rep_f4) the compact tiled form of dist_gemm.hip
     uint8_t *aa_idx = nullptr;    // [n_pad][Lpad16] residue index (20 = gap)
     uint16_t *aa_mask = nullptr;  // [n_pad][Lpad16/16]
     uint8_t *sd_q4 = nullptr;     // scoredist beside a reference image (DevAlign::sd_ref4): the rounded-down table rows of the query's
@@ -342,6 +344,7 @@ struct apples_ctx {
                                        // (api.hip: jc_bound_long_table).  With one: the largest mismatch count whose TABULATED distance
                                        // passes.  The kernel's own exact test decides.  NOT jc_mmax: that one switches k_jc69 onto the table
     int64_t gemm_long_launches = 0;    // launches of k_jc69_gemm_long so far (describe(): "k_split_launches")
+    int64_t cluster_long_launches = 0; // ... over the representatives' image of a clustered context (describe(): "cluster_k_split_launches")
     double *blosum = nullptr;  // 21x21 table (row/col 20 = gap -> 0)
     uint8_t *sd_tq4 = nullptr; // [20][20] fp4 codes of the table rounded down to the grid {0, .5, 1, 1.5, 2, 3, 4, 6} / 4 (dist_sd.hip)
     Workspace ws;
@@ -467,6 +470,11 @@ struct SelectArgs {
     // fused fast path (k_jc69 MODE 1 -> k_select_fast)
     const int32_t *seg_slot, *seg_cnt;  // [nq][stride], [nq][stride/64]
     const double *seg_lut;              // non-null: seg_slot holds position << 26 | valid << 13 | mism, distances are seg_lut[...]
+    // clustered contexts of GEMM_LONG_MIN_L sites and more (cl_long; the LONG forms of k_select_clusters / k_cluster_dist*): the
+    // representatives' pass is k_jc69_gemm_long, which leaves k_jc69 MODE 1's format -- seg_slot holds representative INDICES and
+    // rep_seg_d their fp64 distances, rows of rep_stride entries -- and every distance is jc69_from_counts(..., seg_lut), the table
+    // only where the caller still supplies one
+    const double *rep_seg_d; int cl_long;
     const int32_t *seg_surv;            // non-null (dist_sd.hip): the segments hold CANDIDATES, the ones that failed marked by a negative
                                         // distance; seg_surv[query] = how many passed
     // k_select_fast behind a matrix-core pass over reference rows with bytes beyond ACGT- (DevAlign::ex_off): the survivors on such
@@ -570,8 +578,12 @@ bool dist_gemm_usable(const apples_ctx *ctx);
 int launch_counts_gemm(apples_ctx *ctx, const QueryBlock &qb, int64_t q0, int64_t nq, int32_t *seg_slot, int32_t *seg_cnt);
 // k_jc69_gemm_long: the fused pass of 2-plane blocks on alignments of GEMM_LONG_MIN_L sites and more; writes k_jc69 MODE 1's format
 bool dist_gemm_long_usable(const apples_ctx *ctx);
+// (image / rows: the reference-side operand image and its padded row count -- DevAlign::ref_f4 and slots_pad by default, the
+// representatives' rep_f4 and reps_pad on the clustered route, where seg_slot then names representatives)
 int launch_counts_gemm_long(apples_ctx *ctx, const QueryBlock &qb, int64_t q0, int64_t nq, double *seg_d, int32_t *seg_slot,
-                            int32_t *seg_cnt);
+                            int32_t *seg_cnt, const uint8_t *image = nullptr, int64_t rows = 0);
+// the context keeps compact, tiled fp4 images (a reference or a representative image exists): the query blocks' qf4 are then compact too
+inline bool f4_images_compact(const apples_ctx *ctx) { return ctx->aln.ref_f4 != nullptr || ctx->aln.rep_f4 != nullptr; }
 int launch_counts_fused(apples_ctx *ctx, const QueryBlock &qb, int64_t q0, int64_t nq, int tile, double *seg_d,
                         int32_t *seg_slot, int32_t *seg_cnt);
 int launch_counts_listed(apples_ctx *ctx, const QueryBlock &qb, int64_t q0, int64_t nq_max, const int32_t *qlist,

@@ -529,7 +529,7 @@ int launch_expand_queries_f4(apples_ctx *ctx, const uint8_t *d_raw, int64_t n, u
     if (!st) st = ctx->stream;
     const int64_t total = n_pad * a.G * 2 * 8;
     hipLaunchKernelGGL(k_expand_queries_f4, dim3((unsigned)((total + APPLES_TPB - 1) / APPLES_TPB)), dim3(APPLES_TPB), 0,
-                       st, d_raw, n, a.L, a.G * 2, reinterpret_cast<uint32_t *>(d_out), n_pad, d_src_row, a.ref_f4 != nullptr ? 1 : 0, row0);
+                       st, d_raw, n, a.L, a.G * 2, reinterpret_cast<uint32_t *>(d_out), n_pad, d_src_row, f4_images_compact(ctx) ? 1 : 0, row0);
     HIP_TRY(ctx, hipGetLastError());
     return 0;
 }
@@ -612,7 +612,7 @@ int launch_counts(apples_ctx *ctx, const QueryBlock &qb, int64_t q0, int64_t nq,
     // Full rows stay with the bit-plane kernel: with 8 bytes out per pair and a table lookup per pair the
     // matrix-core form is slower here (0.64 against 0.58 ms at C2 size).  APPLES_DIST_MFMA_ROWS=1 routes
     // tiles of 16 and more queries to it anyway (tests compare its counts with the bytewise definition).
-    if (qb.qf4 && !ctx->aln.ref_f4 && ctx->aln.planes == 2 && !ctx->aln.packed8 && tile >= 16 && knob_on(ctx, "APPLES_DIST_MFMA_ROWS"))
+    if (qb.qf4 && !f4_images_compact(ctx) && ctx->aln.planes == 2 && !ctx->aln.packed8 && tile >= 16 && knob_on(ctx, "APPLES_DIST_MFMA_ROWS"))
         return launch_mfma<0>(ctx, qb, q0, nq, d_dist, d_counts, nullptr, nullptr);
     if (!exact8_rows(ctx, qb)) launch_jc69_tile<2, 0>(ctx, qb, q0, nq, tile, d_dist, d_counts, nullptr, nullptr, nullptr, nullptr);
     else launch_jc69_tile<8, 0>(ctx, qb, q0, nq, tile, d_dist, d_counts, nullptr, nullptr, nullptr, nullptr);

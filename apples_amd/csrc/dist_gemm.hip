@@ -840,9 +840,13 @@ bool dist_gemm_long_usable(const apples_ctx *ctx) {
 }
 
 int launch_counts_gemm_long(apples_ctx *ctx, const QueryBlock &qb, int64_t q0, int64_t nq, double *seg_d, int32_t *seg_slot,
-                            int32_t *seg_cnt) {
+                            int32_t *seg_cnt, const uint8_t *image, int64_t rows) {
     const DevAlign &a = ctx->aln;
-    const int TQ = (int)((nq + GL_QT - 1) / GL_QT), TR = (int)(a.slots_pad / GL_T);
+    if (nq == 0) return 0;
+    const bool reps = image != nullptr;  // the clustered route: the representatives' image, rows of reps_pad entries
+    if (!reps) { image = a.ref_f4; rows = a.slots_pad; }
+    if (rows % GL_T != 0) { ctx->err = "k_jc69_gemm_long: image rows are no multiple of its tile"; return 1; }
+    const int TQ = (int)((nq + GL_QT - 1) / GL_QT), TR = (int)(rows / GL_T);
     if (ctx->n_cu == 0) {
         hipDeviceProp_t prop;
         HIP_TRY(ctx, hipGetDeviceProperties(&prop, ctx->device));
@@ -851,13 +855,13 @@ int launch_counts_gemm_long(apples_ctx *ctx, const QueryBlock &qb, int64_t q0, i
     const int64_t grid = std::max(8, ctx->n_cu / 8 * 8);  // persistent: one workgroup per CU, a multiple of the 8 XCDs
     const int R = (a.G * 2 - 2) % 3;
 #define GL_LAUNCH(R_, T_)                                                                                              \
-    hipLaunchKernelGGL((k_jc69_gemm_long<R_, T_>), dim3((unsigned)grid), dim3(GL_QT * 2), 0, ctx->stream, a.ref_f4, qb.qf4, q0, \
-                       a.slots_pad, a.G * 2, nq, a.L, TQ, TR, seg_slot, seg_cnt, seg_d, ctx->jc_bound_long,            \
+    hipLaunchKernelGGL((k_jc69_gemm_long<R_, T_>), dim3((unsigned)grid), dim3(GL_QT * 2), 0, ctx->stream, image, qb.qf4, q0, \
+                       rows, a.G * 2, nq, a.L, TQ, TR, seg_slot, seg_cnt, seg_d, ctx->jc_bound_long,            \
                        ctx->params.overlap_frac, ctx->params.filt_threshold, ctx->jc_lut)
     if (a.L < GL_TAB) { if (R == 0) GL_LAUNCH(0, true); else if (R == 1) GL_LAUNCH(1, true); else GL_LAUNCH(2, true); }
     else { if (R == 0) GL_LAUNCH(0, false); else if (R == 1) GL_LAUNCH(1, false); else GL_LAUNCH(2, false); }
 #undef GL_LAUNCH
     HIP_TRY(ctx, hipGetLastError());
-    ++ctx->gemm_long_launches;
+    ++(reps ? ctx->cluster_long_launches : ctx->gemm_long_launches);
     return 0;
 }

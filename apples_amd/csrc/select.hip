@@ -704,7 +704,12 @@ __device__ __forceinline__ void cluster_count(const uint4 &rm, const uint4 &r0, 
 //   LDS instead of the bitmap's 33 at 200 000 leaves: five workgroups per CU where the general form has three, and the phase is a
 //   chain of dependent look-ups (its time follows the occupancy: + 1.1 ms per pass with two per CU) -- and lists the queries that need
 //   the general form (a.gen_list), which a LISTED launch takes right behind it.
-template <int PHASE, int CAP = SELECT_CLUSTERS_ACC_CAP, bool LISTED = (PHASE == 4), int TPB = APPLES_TPB, bool SHORT_ONLY = false>
+//   LONG (alignments of GEMM_LONG_MIN_L to 65 535 sites, SelectArgs::cl_long): the representatives' pass was k_jc69_gemm_long, so
+//   the survivors come as representative indices with their fp64 distances in a.rep_seg_d (k_jc69 MODE 1's format) and not as
+//   packed 13-bit counts for a table; by_query keeps the query's first 64 word groups in sh_q as the short form does and takes the
+//   groups beyond from the query's packed tile in global memory -- every lane reads the same address, a broadcast out of L1 / L2 --
+//   and ends in jc69_from_counts (libm's log, or the caller's table where there still is one: 8 192 sites).
+template <int PHASE, int CAP = SELECT_CLUSTERS_ACC_CAP, bool LISTED = (PHASE == 4), int TPB = APPLES_TPB, bool SHORT_ONLY = false, bool LONG = false>
 __global__ __launch_bounds__(TPB) void k_select_clusters(SelectArgs a) {
     constexpr int ACC_CAP = CAP, NW = TPB / WAVE;
     extern __shared__ unsigned long long dyn_bits[];  // [n_words] member bits in slot order, then uint16 [n_words]: the set bits before the
@@ -774,7 +779,7 @@ __global__ __launch_bounds__(TPB) void k_select_clusters(SelectArgs a) {
     const bool sd = PHASE == 4 && a.aa_idx != nullptr;  // scoredist context
     if ((PHASE == 0 || PHASE == 4) && !sd) {
         // the query's packed words (tile layout of pack.hip: [(q/16)*G + g][q%16][plane])
-        for (int i = tid; i < G * 3; i += TPB) {
+        for (int i = tid; i < (LONG && G > 64 ? 64 : G) * 3; i += TPB) {
             const int g = i / 3, pl = i % 3;
             sh_q[i] = a.qpacked[(((q >> 4) * G + g) * 16 + (q & 15)) * 3 + pl];
         }
@@ -817,6 +822,34 @@ __global__ __launch_bounds__(TPB) void k_select_clusters(SelectArgs a) {
     auto by_query = [&](const uint4 *row, int64_t sz) -> double {
         uint32_t nv = 0, nmis = 0;
         int g = 0;
+        if (LONG) {
+            const int Gs = G > 64 ? 64 : G;  // groups of the query in sh_q: the short form's loop over them
+            for (; g + CLUSTER_UNROLL <= Gs; g += CLUSTER_UNROLL) {
+                uint4 w[3 * CLUSTER_UNROLL];
+#pragma unroll
+                for (int k = 0; k < 3 * CLUSTER_UNROLL; ++k) w[k] = row[(int64_t)(g * 3 + k) * sz];
+#pragma unroll
+                for (int k = 0; k < CLUSTER_UNROLL; ++k)
+                    cluster_count(w[3 * k], w[3 * k + 1], w[3 * k + 2], sh_q[(g + k) * 3], sh_q[(g + k) * 3 + 1], sh_q[(g + k) * 3 + 2], nv, nmis);
+            }
+            for (; g < Gs; ++g)
+                cluster_count(row[(int64_t)(g * 3) * sz], row[(int64_t)(g * 3 + 1) * sz], row[(int64_t)(g * 3 + 2) * sz], sh_q[g * 3],
+                              sh_q[g * 3 + 1], sh_q[g * 3 + 2], nv, nmis);
+            // beyond: the query's words from its packed tile, two groups' twelve loads in flight (G - 64 may be odd: the last alone)
+            const uint4 *qw = a.qpacked + ((q >> 4) * G * 16 + (q & 15)) * 3;  // group g, plane pl at (g * 16) * 3 + pl beyond this
+            for (; g + 2 <= G; g += 2) {
+                uint4 w[6], u[6];
+#pragma unroll
+                for (int k = 0; k < 6; ++k) { w[k] = row[(int64_t)(g * 3 + k) * sz]; u[k] = qw[(int64_t)(g + k / 3) * 48 + k % 3]; }
+                cluster_count(w[0], w[1], w[2], u[0], u[1], u[2], nv, nmis);
+                cluster_count(w[3], w[4], w[5], u[3], u[4], u[5], nv, nmis);
+            }
+            if (g < G) {
+                const uint4 *u = qw + (int64_t)g * 48;
+                cluster_count(row[(int64_t)(g * 3) * sz], row[(int64_t)(g * 3 + 1) * sz], row[(int64_t)(g * 3 + 2) * sz], u[0], u[1], u[2], nv, nmis);
+            }
+            return jc69_from_counts(nmis, nv, a.L, a.overlap, a.seg_lut);
+        }
         for (; g + CLUSTER_UNROLL <= G; g += CLUSTER_UNROLL) {  // 3 x CLUSTER_UNROLL loads in flight before the first is used
             uint4 w[3 * CLUSTER_UNROLL];
 #pragma unroll
@@ -860,7 +893,7 @@ __global__ __launch_bounds__(TPB) void k_select_clusters(SelectArgs a) {
         if (at + my <= ACC_CAP) {
             for (int k = 0; k < my; ++k) {
                 const uint32_t pk = (uint32_t)sslot[s * 64 + k];
-                sh_rep[at + k] = (int)(s * 64 + (pk >> 26));
+                sh_rep[at + k] = LONG ? (int)pk : (int)(s * 64 + (pk >> 26));  // (LONG: the representative's index itself)
             }
         } else if (my > 0) {
             overflow = true;
@@ -1166,7 +1199,9 @@ __global__ __launch_bounds__(TPB) void k_select_clusters(SelectArgs a) {
                         double drep = PHASE == 4 ? reprow[rep] : (a.rep_dist ? a.rep_dist[q * a.rep_stride + rep] : 0.0);
                         for (int k = 0; PHASE != 4 && !a.rep_dist && k < cnt[rep >> 6]; ++k) {
                             const uint32_t pk = (uint32_t)sslot[(int64_t)(rep >> 6) * 64 + k];
-                            if ((int)(pk >> 26) == (rep & 63)) {
+                            if (LONG) {
+                                if ((int)pk == rep) drep = a.rep_seg_d[q * a.rep_stride + (int64_t)(rep >> 6) * 64 + k];
+                            } else if ((int)(pk >> 26) == (rep & 63)) {
                                 const long long valid = (pk >> 13) & 0x1fffu, mism = pk & 0x1fffu;
                                 drep = a.seg_lut[valid * (valid + 1) / 2 + mism];
                             }
@@ -1382,7 +1417,10 @@ __global__ __launch_bounds__(CL_TILES_TPB) void k_cluster_tiles(SelectArgs a) {
 // consecutive 16 bytes of the cluster-major panel), the tile's query words are staged in LDS (a wavefront reads one or a few
 // addresses: broadcasts), and the thread adds the pair counts of its up to 16 queries.  Same counts and same table lookup as
 // phase 0 of k_select_clusters, so the same bits.  Persistent workgroups walk the tile table.
+// LONG (alignments of GEMM_LONG_MIN_L to 65 535 sites): the same loops -- 32-bit counts hold any such length -- and every pair's
+// distance from jc69_from_counts in place of the table look-up (the table where the caller still supplies one)
 #define CL_GC 4
+template <bool LONG>
 __global__ __launch_bounds__(APPLES_TPB) void k_cluster_dist(SelectArgs a) {
     __shared__ uint4 sh_qw[64][CL_GC * 3];
     __shared__ int sh_q[64], sh_o[64];
@@ -1442,7 +1480,8 @@ __global__ __launch_bounds__(APPLES_TPB) void k_cluster_dist(SelectArgs a) {
 #else
                     if (j < nqt) {
 #endif
-                        const double d = a.seg_lut[(int64_t)nv[k] * (nv[k] + 1) / 2 + nmis[k]];
+                        const double d = LONG ? jc69_from_counts(nmis[k], nv[k], a.L, a.overlap, a.seg_lut)
+                                              : a.seg_lut[(int64_t)nv[k] * (nv[k] + 1) / 2 + nmis[k]];
                         a.tmp_d[row_start(a.row_off, sh_q[j], a.stride) + sh_o[j] + mc0 + ml] = d;
                         // clade blocks: a member the reference drops, an exact match or the query's own row -- the item goes without
                         if (a.item_bad && (!(d > 0) || (a.self_slot && a.mem_slot[mb + mc0 + ml] == a.self_slot[sh_q[j]]))) a.item_bad[tile.y + j] = 1;
@@ -1466,7 +1505,15 @@ __global__ __launch_bounds__(APPLES_TPB) void k_cluster_dist(SelectArgs a) {
 #ifndef CLM_WAVES
 #define CLM_WAVES 2  // wavefronts per SIMD k_cluster_dist_mfma is compiled for
 #endif
-__global__ __launch_bounds__(WAVE, CLM_WAVES) void k_cluster_dist_mfma(SelectArgs a) {
+// LONG (alignments of GEMM_LONG_MIN_L to 65 535 sites): the main loop is the same -- sum t.t <= 3 x 65 535 and valid <= 65 535 are
+// exact in the two f32 accumulator sets, no split of the K loop -- and the epilogue computes every pair's fp64 distance
+// (jc69_from_counts: libm's log bit for bit, the caller's table at 8 192 sites) where the short form looks it up: all 16 values of a
+// 32 x 32 block first, then their 16 stores, as there.  Sixteen logarithms in flight beside 128 accumulators do not fit two
+// wavefronts per SIMD (80 bytes of scratch per lane at CLM_WAVES = 2, where the short form has 28): the long form is compiled for ONE
+// wavefront per SIMD and uses no scratch ("Clustered route, long forms", has the resource report; the alternative, a second kernel over
+// parked counts, was not built).
+template <bool LONG>
+__global__ __launch_bounds__(WAVE, LONG ? 1 : CLM_WAVES) void k_cluster_dist_mfma(SelectArgs a) {
     // the images of one 64-site block, piece-major: piece (component c, quarter k) of row r -- 8 bytes, 16 sites -- at [c * 4 + k][r].  A lane
     // expands its own row (it holds the row's plane words), so a store instruction writes 64 consecutive pieces and a fragment read
     // 32 consecutive ones: no bank conflicts either way (row-major images as in k_jc69_mfma cost this kernel four-way conflicts on
@@ -1597,8 +1644,11 @@ __global__ __launch_bounds__(WAVE, CLM_WAVES) void k_cluster_dist_mfma(SelectArg
                         const int nv = (int)s2[i][j][x], nmis = (3 * nv - (int)s1[i][j][x]) >> 2;
 #ifdef CL_EXP_NO_EPILOGUE  // (timing experiment: the main loop alone)
                         d[x] = (double)(nv + nmis);
+#elif defined(CL_EXP_NO_LOG)  // (timing experiment, long form: the epilogue's stores without its logarithms -- positive finite values, wrong placements)
+                        d[x] = LONG ? (double)(nv + nmis + 1) : a.seg_lut[(int64_t)nv * (nv + 1) / 2 + nmis];
 #else
-                        d[x] = a.seg_lut[(int64_t)nv * (nv + 1) / 2 + nmis];
+                        d[x] = LONG ? jc69_from_counts((uint32_t)nmis, (uint32_t)nv, a.L, a.overlap, a.seg_lut)
+                                    : a.seg_lut[(int64_t)nv * (nv + 1) / 2 + nmis];
 #endif
                     }
 #pragma unroll
@@ -1706,7 +1756,12 @@ __global__ __launch_bounds__(APPLES_TPB) void k_cluster_dist_sd(SelectArgs a) {
     }
 }
 
-int launch_select_clusters(apples_ctx *ctx, const SelectArgs &a, int64_t nq) {
+// (LONG: SelectArgs::cl_long -- the same launches with the kernels' long forms)
+template <bool LONG, int PHASE, int CAP = SELECT_CLUSTERS_ACC_CAP, bool LISTED = (PHASE == 4), int TPB = APPLES_TPB, bool SHORT_ONLY = false>
+static constexpr auto ksc() { return &k_select_clusters<PHASE, CAP, LISTED, TPB, SHORT_ONLY, LONG>; }
+
+template <bool LONG>
+static int launch_select_clusters_t(apples_ctx *ctx, const SelectArgs &a, int64_t nq) {
     if (nq == 0) return 0;
     // the slot bitmap and its 16-bit in-run prefixes (runs of 16 words: 262 144 slots); with clade blocks over emission indices
     size_t dyn = (size_t)(((a.e_of_slot ? std::max(a.n_e, a.n_members) : a.n_members) + 63) >> 6) * 10;
@@ -1715,18 +1770,18 @@ int launch_select_clusters(apples_ctx *ctx, const SelectArgs &a, int64_t nq) {
     const bool sd = a.aa_idx != nullptr;  // scoredist context: k_cluster_dist_sd computes the member distances (no by-query form)
     const bool by_query = (ctx->dbg & APPLES_DBG_CLUSTER_BY_QUERY) != 0 && !sd;  // diagnostic switch: phase 0 alone
     if (dyn > 48 * 1024) {  // (beyond the default allowance of dynamic LDS -- references of more than ~300 000 slots; per device, so asked for at every launch)
-        HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_select_clusters<0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
-        HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_select_clusters<3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
-        HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_select_clusters<3, SELECT_CLUSTERS_ACC_CAP, true, APPLES_TPB>),
+        HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(ksc<LONG, 0>()), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
+        HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(ksc<LONG, 3>()), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
+        HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(ksc<LONG, 3, SELECT_CLUSTERS_ACC_CAP, true, APPLES_TPB>()),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
-        HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_select_clusters<3, SELECT_CLUSTERS_BIG_CAP, true, 1024>),
+        HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(ksc<LONG, 3, SELECT_CLUSTERS_BIG_CAP, true, 1024>()),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
-        HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_select_clusters<3, SELECT_CLUSTERS_HUGE_CAP, true, 1024>),
+        HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(ksc<LONG, 3, SELECT_CLUSTERS_HUGE_CAP, true, 1024>()),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
     }
     if (sd && !a.cl_count) { ctx->err = "scoredist cluster route without its tile scratch"; return 1; }
     if (by_query || !a.cl_count) {
-        hipLaunchKernelGGL(k_select_clusters<0>, dim3((unsigned)nq), dim3(APPLES_TPB), dyn, ctx->stream, a);
+        hipLaunchKernelGGL((ksc<LONG, 0>()), dim3((unsigned)nq), dim3(APPLES_TPB), dyn, ctx->stream, a);
         HIP_TRY(ctx, hipGetLastError());
         return 0;
     }
@@ -1737,13 +1792,13 @@ int launch_select_clusters(apples_ctx *ctx, const SelectArgs &a, int64_t nq) {
     b.qlist = a.big_list; b.qcount = a.big_count;
     const dim3 gbig((unsigned)std::min<int64_t>(nq, SELECT_CLUSTERS_BIG_LIST));
     if (big) HIP_TRY(ctx, hipMemsetAsync(a.big_count, 0, sizeof(int32_t), ctx->stream));
-    hipLaunchKernelGGL(k_select_clusters<1>, dim3((unsigned)nq), dim3(APPLES_TPB), 0, ctx->stream, a);
-    if (huge) hipLaunchKernelGGL((k_select_clusters<1, HUGE, true>), gbig, dim3(APPLES_TPB), 0, ctx->stream, b);
-    else if (big) hipLaunchKernelGGL((k_select_clusters<1, BIG, true>), gbig, dim3(APPLES_TPB), 0, ctx->stream, b);
+    hipLaunchKernelGGL((ksc<LONG, 1>()), dim3((unsigned)nq), dim3(APPLES_TPB), 0, ctx->stream, a);
+    if (huge) hipLaunchKernelGGL((ksc<LONG, 1, HUGE, true>()), gbig, dim3(APPLES_TPB), 0, ctx->stream, b);
+    else if (big) hipLaunchKernelGGL((ksc<LONG, 1, BIG, true>()), gbig, dim3(APPLES_TPB), 0, ctx->stream, b);
     hipLaunchKernelGGL(k_cluster_tiles, dim3(1), dim3(CL_TILES_TPB), 0, ctx->stream, a);
-    hipLaunchKernelGGL(k_select_clusters<2>, dim3((unsigned)nq), dim3(APPLES_TPB), 0, ctx->stream, a);
-    if (huge) hipLaunchKernelGGL((k_select_clusters<2, HUGE, true>), gbig, dim3(APPLES_TPB), 0, ctx->stream, b);
-    else if (big) hipLaunchKernelGGL((k_select_clusters<2, BIG, true>), gbig, dim3(APPLES_TPB), 0, ctx->stream, b);
+    hipLaunchKernelGGL((ksc<LONG, 2>()), dim3((unsigned)nq), dim3(APPLES_TPB), 0, ctx->stream, a);
+    if (huge) hipLaunchKernelGGL((ksc<LONG, 2, HUGE, true>()), gbig, dim3(APPLES_TPB), 0, ctx->stream, b);
+    else if (big) hipLaunchKernelGGL((ksc<LONG, 2, BIG, true>()), gbig, dim3(APPLES_TPB), 0, ctx->stream, b);
     if (ctx->n_cu == 0) {
         hipDeviceProp_t prop;
         HIP_TRY(ctx, hipGetDeviceProperties(&prop, ctx->device));
@@ -1751,16 +1806,16 @@ int launch_select_clusters(apples_ctx *ctx, const SelectArgs &a, int64_t nq) {
     }
     const int per_cu = (int)knob(ctx, "APPLES_CLUSTER_WGS", 8);  // tuning knob
     if (sd) hipLaunchKernelGGL(k_cluster_dist_sd<4>, dim3((unsigned)(ctx->n_cu * std::max(per_cu, 1))), dim3(APPLES_TPB), 0, ctx->stream, a);
-    else if (a.cl_mfma) hipLaunchKernelGGL(k_cluster_dist_mfma, dim3((unsigned)(ctx->n_cu * 4 * CLM_WAVES)), dim3(WAVE), 0, ctx->stream, a);  // (18 KB of LDS per wavefront: eight per CU)
-    else hipLaunchKernelGGL(k_cluster_dist, dim3((unsigned)(ctx->n_cu * std::max(per_cu, 1))), dim3(APPLES_TPB), 0, ctx->stream, a);
+    else if (a.cl_mfma) hipLaunchKernelGGL(k_cluster_dist_mfma<LONG>, dim3((unsigned)(ctx->n_cu * 4 * (LONG ? 1 : CLM_WAVES))), dim3(WAVE), 0, ctx->stream, a);  // (18 KB of LDS per wavefront: eight per CU)
+    else hipLaunchKernelGGL(k_cluster_dist<LONG>, dim3((unsigned)(ctx->n_cu * std::max(per_cu, 1))), dim3(APPLES_TPB), 0, ctx->stream, a);
     // the second form's last phase beside the first's, on the spare stream: a hundred-odd workgroups of 1 024 threads (their
     // rounds of member lookups are what such a workgroup takes: a quarter of the rounds of 256 threads) leave the chip idle
     if (a.blk_tiles) HIP_TRY(ctx, hipEventRecord(ctx->ev_blk[0], ctx->stream));
     if (big) {
         HIP_TRY(ctx, hipEventRecord(ctx->ev_cl[0], ctx->stream));
         HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_cl[0], 0));
-        if (huge) hipLaunchKernelGGL((k_select_clusters<3, HUGE, true, 1024>), gbig, dim3(1024), dyn, ctx->stream2, b);
-        else hipLaunchKernelGGL((k_select_clusters<3, BIG, true, 1024>), gbig, dim3(1024), dyn, ctx->stream2, b);
+        if (huge) hipLaunchKernelGGL((ksc<LONG, 3, HUGE, true, 1024>()), gbig, dim3(1024), dyn, ctx->stream2, b);
+        else hipLaunchKernelGGL((ksc<LONG, 3, BIG, true, 1024>()), gbig, dim3(1024), dyn, ctx->stream2, b);
         HIP_TRY(ctx, hipEventRecord(ctx->ev_cl[1], ctx->stream2));
     }
     // clade blocks: the S tuples inside them (k_blocks_up), on the sweep's side stream beside the last phase, which names their
@@ -1791,14 +1846,19 @@ int launch_select_clusters(apples_ctx *ctx, const SelectArgs &a, int64_t nq) {
         SelectArgs g = a;
         g.qlist = a.gen_list; g.qcount = a.gen_count;
         HIP_TRY(ctx, hipMemsetAsync(a.gen_count, 0, sizeof(int32_t), ctx->stream));
-        hipLaunchKernelGGL((k_select_clusters<3, SELECT_CLUSTERS_ACC_CAP, false, APPLES_TPB, true>), dim3((unsigned)nq), dim3(APPLES_TPB), dyn_short, ctx->stream, a);
-        hipLaunchKernelGGL((k_select_clusters<3, SELECT_CLUSTERS_ACC_CAP, true, APPLES_TPB>), dim3((unsigned)nq), dim3(APPLES_TPB), dyn, ctx->stream, g);
+        hipLaunchKernelGGL((ksc<LONG, 3, SELECT_CLUSTERS_ACC_CAP, false, APPLES_TPB, true>()), dim3((unsigned)nq), dim3(APPLES_TPB), dyn_short, ctx->stream, a);
+        hipLaunchKernelGGL((ksc<LONG, 3, SELECT_CLUSTERS_ACC_CAP, true, APPLES_TPB>()), dim3((unsigned)nq), dim3(APPLES_TPB), dyn, ctx->stream, g);
     } else
-    hipLaunchKernelGGL(k_select_clusters<3>, dim3((unsigned)nq), dim3(APPLES_TPB), dyn, ctx->stream, a);
+    hipLaunchKernelGGL((ksc<LONG, 3>()), dim3((unsigned)nq), dim3(APPLES_TPB), dyn, ctx->stream, a);
     if (!blk_first && launch_blk()) return 1;
     if (big) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_cl[1], 0));
     HIP_TRY(ctx, hipGetLastError());
     return 0;
+}
+
+int launch_select_clusters(apples_ctx *ctx, const SelectArgs &a, int64_t nq) {
+    if (a.cl_long && (!a.rep_seg_d || a.aa_idx)) { ctx->err = "clustered long route without the representatives' distances"; return 1; }
+    return a.cl_long ? launch_select_clusters_t<true>(ctx, a, nq) : launch_select_clusters_t<false>(ctx, a, nq);
 }
 
 // The slow list of the clustered fast path (fewer than `-b` valid member distances inside the threshold): phase 4 computes the
@@ -1815,9 +1875,11 @@ int launch_select_clusters_listed(apples_ctx *ctx, const SelectArgs &a, int64_t 
         b.rep_cache = 0;
         dyn = (n_words + (n_words + 3) / 4) * 8;
     }
+    const void *fn = a.cl_long ? reinterpret_cast<const void *>(ksc<true, 4>()) : reinterpret_cast<const void *>(ksc<false, 4>());
     if (dyn > 48 * 1024)  // (beyond the default allowance of dynamic LDS; per device, so asked for at every launch)
-        HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_select_clusters<4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
-    hipLaunchKernelGGL(k_select_clusters<4>, dim3((unsigned)std::min<int64_t>(nq_max, 1024)), dim3(APPLES_TPB), dyn, ctx->stream, b);
+        HIP_TRY(ctx, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
+    if (a.cl_long) hipLaunchKernelGGL((ksc<true, 4>()), dim3((unsigned)std::min<int64_t>(nq_max, 1024)), dim3(APPLES_TPB), dyn, ctx->stream, b);
+    else hipLaunchKernelGGL((ksc<false, 4>()), dim3((unsigned)std::min<int64_t>(nq_max, 1024)), dim3(APPLES_TPB), dyn, ctx->stream, b);
     HIP_TRY(ctx, hipGetLastError());
     return 0;
 }
