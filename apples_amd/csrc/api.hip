@@ -856,7 +856,7 @@ void free_workspace(Workspace &w) {
     dev_free(w.dist); dev_free(w.counts); dev_free(w.obs_node); dev_free(w.obs_dist); dev_free(w.cnt_gt);
     dev_free(w.n_obs); dev_free(w.overflow_list); dev_free(w.route_list);
     dev_free(w.cls_list); dev_free(w.cls_count); dev_free(w.seg_slot); dev_free(w.seg_cnt);
-    dev_free(w.dist_slow); dev_free(w.slow_list); dev_free(w.row_off);
+    dev_free(w.dist_slow); dev_free(w.slow_list); dev_free(w.row_off); dev_free(w.seg_slot2); dev_free(w.seg_cnt2);
     free_sweep(w.small);
     free_sweep(w.big);
     w = Workspace();
@@ -938,7 +938,7 @@ int alloc_sweep(apples_ctx *ctx, Workspace::Sweep &sw, int wgs, int teams_per_wg
 // for config 3's 100 000 queries, not seven (every kernel of the route has a tail of a few hundred microseconds per batch).
 int ensure_workspace(apples_ctx *ctx, int64_t members, int64_t stride, int64_t want_batch, bool need_dist,
                      bool need_counts, bool need_xe, bool need_fused = false, bool need_alt = false, bool slim = false,
-                     int64_t seg_stride = 0, bool want_ragged = false) {
+                     int64_t seg_stride = 0, bool want_ragged = false, bool seg2_if_multi = false) {
     Workspace &w = ctx->ws;
     const DevTree &t = ctx->tree;
     int64_t batch = want_batch;
@@ -949,6 +949,12 @@ int ensure_workspace(apples_ctx *ctx, int64_t members, int64_t stride, int64_t w
     int64_t per_q = stride * 8 + members * 12 + (int64_t)(t.height + 2) * 4 + (need_counts ? stride * 4 : 0) +
                     (need_fused ? stride * 12 + stride / 16 : 0);
     if (slim) per_q = stride * 4 + stride / 16 + stride * 2 + members * 12 + (int64_t)(t.height + 2) * 4;
+    // `seg2_if_multi` (the overlapped driver, run_block_main): where the block takes more than one device batch, a second set of
+    // seg_slot / seg_cnt -- the distance pass of batch b + 1 writes it while the selection of batch b reads the first.  Nothing else
+    // exists twice: every other buffer of a batch is written and read by kernels of the back stream, one batch after the other.
+    const int64_t seg2_per_q = stride * 4 + stride / 16;
+    bool seg2 = slim && w.seg_slot2 != nullptr;
+    if (seg2) per_q += seg2_per_q;
     if (cslim) per_q = stride * 8 + stride + seg_stride * 4 + seg_stride / 16 + members * 12 + (int64_t)(t.height + 2) * 4;
     // ragged rows (common.h, Workspace::ragged): the clustered fused route on the lean sweep, a reference of at least four small rows
     const int64_t row_small = knob(ctx, "APPLES_RAGGED_SMALL", 16384);  // (test knob: small rows that send many queries to the big ones)
@@ -999,8 +1005,13 @@ int ensure_workspace(apples_ctx *ctx, int64_t members, int64_t stride, int64_t w
         return round_up(std::max<int64_t>(b, 1), 32);
     };
     batch = size_batch();
+    if (slim && seg2_if_multi && !seg2 && batch < want_batch) {
+        seg2 = true;
+        per_q += seg2_per_q;
+        batch = size_batch();
+    }
     bool regrow = batch > w.batch || members > w.obs_cap || stride > w.stride || (need_counts && !w.counts) ||
-                  (need_xe && !w.big.xe) || (need_dist && !w.dist) || (need_fused && !w.seg_slot) || (need_alt && !w.has_alt) ||
+                  (need_xe && !w.big.xe) || (need_dist && !w.dist) || (need_fused && !w.seg_slot) || (need_alt && !w.has_alt) || (seg2 && !w.seg_slot2) ||
                   // full rows wanted where only a slice exists (run_block steps by w.batch) -- unless the whole block fits the slice
                   // (a slim workspace serves the few queries of an exact8 block as it is: no regrowing back and forth)
                   (!slim && !cslim && w.dist_rows < std::min(w.batch, round_up(std::max<int64_t>(want_batch, 1), 32))) ||
@@ -1068,6 +1079,10 @@ int ensure_workspace(apples_ctx *ctx, int64_t members, int64_t stride, int64_t w
         if (alt && set == 0) swap_bufs(w);
     }
     w.has_alt = alt;
+    if (seg2) {
+        if (dev_alloc(ctx, &w.seg_slot2, batch * seg_w)) return 1;
+        if (dev_alloc(ctx, &w.seg_cnt2, batch * std::max<int64_t>(seg_w / 64, 1))) return 1;
+    }
     // small teams: one wavefront per query, up to 8 workgroups (32 waves) per CU on 256 CUs;
     // map is n_nodes ints per team (<= ~8 GiB in total), order/S/R share ~16 GiB
     int64_t nn = t.n_nodes;
@@ -1494,9 +1509,15 @@ int dist_tile_for(const apples_ctx *ctx, int64_t nq) {
 }
 
 // One pass of the hot path over a resident query block.  The block is cut into sub-batches that
-// run distance -> selection -> sweep back to back on one stream (default).  With APPLES_PIPELINE > 1
-// they flow through two streams instead (front = distance + selection, back = sweep, two sets of
-// batch buffers); measured slower on MI355X, kept as an experiment knob.
+// run distance -> selection -> sweep back to back on one stream.
+// The overlapped route (a singleton JC69 context on the 2-plane GEMM pass, MLSE / ME on the level sweep, two device batches or
+// more; APPLES_OVERLAP=0 / 1 forces the choice either way where the route applies): the distance GEMM of batch b + 1 runs on the front
+// stream while selection, top-up chain and sweep of batch b run on the back stream.  GEMM(0) is the full form; every later one is
+// the sharing form (dist_gemm.hip: one four-wavefront workgroup per CU, half the registers), enqueued directly behind its
+// predecessor so that its persistent workgroups land first and the back stream's kernels fill what is left of every CU.  Only
+// seg_slot / seg_cnt exist twice (ensure_workspace); the slim rows, the split first chunk, the top-up overlap of small batches and
+// the equal, 256-aligned sub-batches stay as on the serial route.  None of the back stream's kernels waits for another workgroup
+// (their queues are atomic cursors: DESIGN.md section 4), so reduced residency beside the GEMM cannot hang them.
 // `feed` (optional): the block's queries are still in the caller's host buffer.  Chunk i = the queries of
 // sub-batch i is uploaded and packed on stream2 while the main stream works on sub-batch i - 1, so that
 // the copy hides behind the kernels (apples_place_from_sequences: host buffer in, host buffer out).
@@ -1504,13 +1525,16 @@ struct Feeder {
     const uint8_t *host;
 };
 
-// the back stream of the pipeline experiments, made on first use
+// the back stream of the overlapped route (and of the table route's pipeline experiment), made on first use
 int back_stream(apples_ctx *ctx) {
     if (!ctx->stream3) HIP_TRY(ctx, hipStreamCreate(&ctx->stream3));
     return 0;
 }
 
 int run_block_main(apples_ctx *ctx, QueryBlock &qb, const Feeder *feed);
+
+// the overlapped route where it applies and APPLES_OVERLAP does not say (measured: profiles/overlap_c3.txt)
+constexpr bool OVERLAP_DEFAULT = true;
 
 // ragged rows (common.h, Workspace::ragged): every query of the device batch starts on its small row
 __global__ void k_row_init(int64_t *__restrict__ row_off, int64_t nq, int64_t row_small) {
@@ -1550,7 +1574,6 @@ int run_block_main(apples_ctx *ctx, QueryBlock &qb, const Feeder *feed) {
     // fused path: threshold compaction in the distance kernel's epilogue; only queries that need
     // the top-up rule get full distance rows
     const bool no_fuse = (ctx->dbg & APPLES_DBG_NO_FUSE) != 0;  // diagnostic switch
-    const int n_pipe = (int)knob(ctx, "APPLES_PIPELINE", 1);  // >1: measured slower (sweep and distance kernels contend), kept as a knob
     // clustered references: the matrix-core pass runs over the representatives only, k_select_clusters expands
     // the accepted clusters (needs the panels of setup_alignment, the tabulated distances and their integer
     // threshold form)
@@ -1567,26 +1590,32 @@ int run_block_main(apples_ctx *ctx, QueryBlock &qb, const Feeder *feed) {
     // scoredist with singleton clusters: threshold compaction in the distance kernel's epilogue as well
     const bool sfused = !no_fuse && a.all_singleton && ctx->params.model == APPLES_SCOREDIST;
     const bool fused = !no_fuse && (((a.all_singleton || cfused) && ctx->params.model == APPLES_JC69) || sfused || csd);
-    const bool pipelined = n_pipe > 1 && qb.n >= 1024;
-    int64_t want = qb.n;
-    if (pipelined) want = round_up((qb.n + n_pipe - 1) / n_pipe, 32);
+    const int64_t want = qb.n;
     // (clustered references on the fused route keep full rows per query: with their member distances parked in the tail of
     // the query's own observation row and 4 device batches of 25 000 in place of 7 of 14 300 the pass measured 80.5 ms
     // against 69.2 -- lists of 3 126 observed leaves per query outgrow the Infinity Cache in the bigger batches -- and the
     // selection kernel's load schedule suffered from the second home of the distances: 4.0 against 2.6 ms per batch)
-    const bool slim = fused && a.all_singleton && fused_counts_format(ctx, qb) && !pipelined;
-    if (ensure_workspace(ctx, a.n_refs, a.slots_pad, want, true, false, hybrid, fused, pipelined, slim,
-                         (cfused && !pipelined && !(ctx->dbg & APPLES_DBG_NO_CLUSTER_TOPUP)) ? a.reps_pad : 0,
-                         cfused && !pipelined && !hybrid && !(ctx->dbg & APPLES_DBG_CLUSTER_BY_QUERY))) return 1;
+    const bool slim = fused && a.all_singleton && fused_counts_format(ctx, qb);
+    // the overlapped route applies (comment above; APPLES_EXOTIC_FIX_KERNEL, a diagnostic, puts a kernel that writes the batch's
+    // n_obs behind the GEMM: serial)
+    const long long ovl_knob = knob(ctx, "APPLES_OVERLAP", -1);
+    const bool ovl_ok = slim && !cfused && !sfused && ctx->params.model == APPLES_JC69 && dist_gemm_usable(ctx) && a.L <= GEMM_MAX_L13 && !hybrid && !ctx->tree.scan &&
+                        !knob_on(ctx, "APPLES_EXOTIC_FIX_KERNEL") && (ovl_knob < 0 ? OVERLAP_DEFAULT : ovl_knob != 0);
+    if (ensure_workspace(ctx, a.n_refs, a.slots_pad, want, true, false, hybrid, fused, false, slim,
+                         (cfused && !(ctx->dbg & APPLES_DBG_NO_CLUSTER_TOPUP)) ? a.reps_pad : 0,
+                         cfused && !hybrid && !(ctx->dbg & APPLES_DBG_CLUSTER_BY_QUERY), ovl_ok)) return 1;
     Workspace &w = ctx->ws;
     if (w.ragged) HIP_TRY(ctx, hipMemsetAsync(ctx->d_rag, 0, 2 * sizeof(int32_t), ctx->stream));
-    int64_t step = pipelined ? std::min<int64_t>(w.batch, want) : w.batch;
+    int64_t step = w.batch;
     const int64_t n_sub = (qb.n + step - 1) / step;
-    if (!pipelined && n_sub > 1) step = std::min(step, round_up((qb.n + n_sub - 1) / n_sub, 32));  // equal sub-batches
+    if (n_sub > 1) step = std::min(step, round_up((qb.n + n_sub - 1) / n_sub, 32));  // equal sub-batches
     // (the GEMM-form distance pass reads whole contiguous kilobytes when a sub-batch starts on a 256-row image tile)
-    if (!pipelined && n_sub > 1 && step >= 2048 && dist_gemm_usable(ctx) && round_up(step, 256) <= w.batch) step = round_up(step, 256);
-    if (pipelined && back_stream(ctx)) return 1;
-    hipStream_t front = ctx->stream, back = pipelined ? ctx->stream3 : ctx->stream;
+    if (n_sub > 1 && step >= 2048 && dist_gemm_usable(ctx) && round_up(step, 256) <= w.batch) step = round_up(step, 256);
+    const bool ovl = ovl_ok && n_sub >= 2 && w.slim && w.seg_slot2;
+    ctx->overlap = ovl ? 1 : 0;
+    ctx->overlap_batches = ovl ? (int)n_sub : 0;
+    if (ovl && back_stream(ctx)) return 1;
+    hipStream_t front = ctx->stream, back = ovl ? ctx->stream3 : ctx->stream;
     // timing events come from a pool that lives with the context (creating and destroying a dozen
     // events per call costs host time inside every pass)
     while (ctx->ev_pool.size() < (size_t)n_sub * 8 + 2) {
@@ -1601,7 +1630,7 @@ int run_block_main(apples_ctx *ctx, QueryBlock &qb, const Feeder *feed) {
     // take any range of query rows): the first quarter is on the device and under way while the rest is still on the bus
     // (a 12 500-query chunk of config 3: 0.22 ms of copy + 0.08 ms of packing in front of 3.6 ms of GEMM).  head(nq) = rows of
     // the first piece (nq: one piece).
-    const bool split_feed = feed && fused && !cfused && !pipelined && ((sfused && qb.sd_q4 && sd_gemm_usable(ctx)) ||
+    const bool split_feed = feed && fused && !cfused && ((sfused && qb.sd_q4 && sd_gemm_usable(ctx)) ||
                                                                         (!sfused && fused_counts_format(ctx, qb) && dist_gemm_usable(ctx)));
     auto head = [&](int64_t nq) -> int64_t { return split_feed && nq >= 4096 ? round_up(nq / 4, 256) : nq; };
     // upload + pack sub-batch i on stream2, an event behind each piece.  The copy of a pageable host buffer holds the calling
@@ -1635,7 +1664,7 @@ int run_block_main(apples_ctx *ctx, QueryBlock &qb, const Feeder *feed) {
         if (feed_head(0)) return 1;
     }
     HIP_TRY(ctx, hipEventRecord(e_start, front));
-    if (pipelined) HIP_TRY(ctx, hipStreamWaitEvent(back, e_start, 0));
+    if (ovl) HIP_TRY(ctx, hipStreamWaitEvent(back, e_start, 0));
     int launches = 0;
     std::vector<char> sd_filter_timed((size_t)n_sub, 0), blk_timed((size_t)n_sub, 0);  // per sub-batch: e[5] was recorded (the scoredist filter ran there)
     // The queries on the top-up / slow list get full distance rows; a slim workspace holds rows for a slice of the batch
@@ -1663,21 +1692,55 @@ int run_block_main(apples_ctx *ctx, QueryBlock &qb, const Feeder *feed) {
             if (fn(list + (int64_t)k * R, n_sl > 1 ? ctx->d_slice_cnt + k : count, lens[k])) return 1;
         return 0;
     };
+    // The overlapped route's distance pass of sub-batch i: on the front stream, into set i & 1 of seg_slot / seg_cnt, behind the
+    // chunk's feed and behind the back stream's work on sub-batch i - 2, which read that set.  The first chunk of a host buffer in
+    // two pieces, as on the serial route.
+    int seg_view = 0;  // the set w.seg_slot / w.seg_cnt name
+    int32_t *const seg_s[2] = {w.seg_slot, w.seg_slot2}, *const seg_c[2] = {w.seg_cnt, w.seg_cnt2};
+    auto ovl_gemm = [&](int64_t i) -> int {
+        const int64_t q0 = i * step, nq = std::min(step, qb.n - q0), nh = (feed && i == 0) ? head(nq) : nq;
+        const int set = (int)(i & 1);
+        const bool share = i > 0;  // (nothing runs beside the first)
+        hipEvent_t *e = &ev[(size_t)i * 8];
+        if (feed) HIP_TRY(ctx, hipStreamWaitEvent(front, ctx->ev_feed[2 * i + (nh < nq ? 0 : 1)], 0));
+        if (i >= 2) HIP_TRY(ctx, hipStreamWaitEvent(front, ctx->ev_back[set], 0));
+        HIP_TRY(ctx, hipEventRecord(e[0], front));
+        HIP_TRY(ctx, hipMemsetAsync(seg_c[set], 0, (size_t)nq * (w.stride / 64) * sizeof(int32_t), front));  // the kernel writes only the non-empty segments' counts
+        if (launch_counts_gemm(ctx, qb, q0, nh, seg_s[set], seg_c[set], share)) return 1;
+        if (nh < nq) {  // the rest of the chunk travels meanwhile
+            if (feed_rest(i)) return 1;
+            HIP_TRY(ctx, hipStreamWaitEvent(front, ctx->ev_feed[2 * i + 1], 0));
+            if (launch_counts_gemm(ctx, qb, q0 + nh, nq - nh, seg_s[set] + nh * w.stride, seg_c[set] + nh * (w.stride / 64), share)) return 1;
+            ++launches;
+        }
+        HIP_TRY(ctx, hipEventRecord(e[1], front));
+        HIP_TRY(ctx, hipEventRecord(ctx->ev_front[set], front));
+        ++launches;
+        return 0;
+    };
     for (int64_t i = 0; i < n_sub; ++i) {
         const int64_t q0 = i * step;
         const int64_t nq = std::min(step, qb.n - q0);
         const int set = (int)(i & 1);
-        if (pipelined && i > 0) swap_bufs(w);  // host view: w.* now names buffer set `set`
-        if (pipelined && i >= 2) HIP_TRY(ctx, hipStreamWaitEvent(front, ctx->ev_back[set], 0));  // set free again
         hipEvent_t *e = &ev[(size_t)i * 8];
+        if (ovl) {
+            // GEMM(i + 1) goes out directly behind GEMM(i), before anything of batch i reaches the back stream; chunk i + 1 of a host
+            // buffer was sent while batch i - 1 was enqueued (chunk 1: here, behind GEMM(0))
+            if (i == 0 && (ovl_gemm(0) || (feed && feed_chunk(1)))) return 1;
+            if (i + 1 < n_sub && ovl_gemm(i + 1)) return 1;
+            HIP_TRY(ctx, hipStreamWaitEvent(back, ctx->ev_front[set], 0));
+            if (seg_view != set) { std::swap(w.seg_slot, w.seg_slot2); std::swap(w.seg_cnt, w.seg_cnt2); seg_view = set; }
+        }
+        // selection, top-up chain and sweep: on the back stream of the overlapped route, else on the one stream
+        StreamScope sel_scope(ctx, back);
         ctx->cur_batch_queries = nq;  // (route_threshold)
         // rows of the chunk's first piece.  Only the first chunk is still on the bus when its kernels could start: chunk i + 1
         // travels while batch i runs and is there, whole, when its turn comes -- one launch then, not two
         const int64_t nh = (feed && i == 0) ? head(nq) : nq;
-        if (feed) HIP_TRY(ctx, hipStreamWaitEvent(front, ctx->ev_feed[2 * i + (nh < nq ? 0 : 1)], 0));  // chunk i (its first piece) is on the device
-        HIP_TRY(ctx, hipMemsetAsync(w.cls_count, 0, 64 * sizeof(int32_t), front));  // every counter of the batch
+        if (feed && !ovl) HIP_TRY(ctx, hipStreamWaitEvent(front, ctx->ev_feed[2 * i + (nh < nq ? 0 : 1)], 0));  // chunk i (its first piece) is on the device
+        HIP_TRY(ctx, hipMemsetAsync(w.cls_count, 0, 64 * sizeof(int32_t), back));  // every counter of the batch
         if (w.ragged) {  // every query's rows: the small ones (common.h, Workspace::ragged)
-            hipLaunchKernelGGL(k_row_init, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, front, w.row_off, nq, w.row_small);
+            hipLaunchKernelGGL(k_row_init, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, back, w.row_off, nq, w.row_small);
             HIP_TRY(ctx, hipGetLastError());
         }
         // The top-up chain -- full rows (or rows of bounds) for the queries k_select_fast listed, their selection -- runs BESIDE the
@@ -1691,17 +1754,17 @@ int run_block_main(apples_ctx *ctx, QueryBlock &qb, const Feeder *feed) {
         // sweeps get in each other's way (config 3: 48.1 -> 49.7 ms, config 4: 23.0 -> 23.6).
         bool swept_here = false;
         auto overlapped = [&](SelectArgs &sa, auto chain) -> int {
-            const bool on = !pipelined && !hybrid && !(ctx->dbg & APPLES_DBG_NO_TOPUP_OVERLAP) && !ctx->tree.scan && w.small.lean &&
+            const bool on = !hybrid && !(ctx->dbg & APPLES_DBG_NO_TOPUP_OVERLAP) && !ctx->tree.scan && w.small.lean &&
                             w.small.lean_leaf && w.big.lean && nq <= LEAN_SMALL_BATCH;
             if (!on) {
                 if (chain()) return 1;
-                HIP_TRY(ctx, hipEventRecord(e[2], front));
+                HIP_TRY(ctx, hipEventRecord(e[2], back));
                 return 0;
             }
-            HIP_TRY(ctx, hipEventRecord(e[2], front));  // (the selection phase of the timers: k_select_fast alone)
-            HIP_TRY(ctx, hipEventRecord(ctx->ev_top[0], front));
-            HIP_TRY(ctx, hipEventRecord(e[3], front));
-            if (run_sweep(ctx, qb.out + q0, nq, front, 1)) return 1;
+            HIP_TRY(ctx, hipEventRecord(e[2], back));  // (the selection phase of the timers: k_select_fast alone)
+            HIP_TRY(ctx, hipEventRecord(ctx->ev_top[0], back));
+            HIP_TRY(ctx, hipEventRecord(e[3], back));
+            if (run_sweep(ctx, qb.out + q0, nq, back, 1)) return 1;
             {
                 StreamScope scope(ctx, ctx->stream2);
                 HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_top[0], 0));
@@ -1711,9 +1774,9 @@ int run_block_main(apples_ctx *ctx, QueryBlock &qb, const Feeder *feed) {
                 if (run_sweep_second(ctx, qb.out + q0, nq, ctx->stream2)) return 1;
                 HIP_TRY(ctx, hipEventRecord(ctx->ev_top[1], ctx->stream2));
             }
-            HIP_TRY(ctx, hipStreamWaitEvent(front, ctx->ev_top[1], 0));
-            if (run_sweep(ctx, qb.out + q0, nq, front, 2)) return 1;
-            HIP_TRY(ctx, hipEventRecord(e[4], front));
+            HIP_TRY(ctx, hipStreamWaitEvent(back, ctx->ev_top[1], 0));
+            if (run_sweep(ctx, qb.out + q0, nq, back, 2)) return 1;
+            HIP_TRY(ctx, hipEventRecord(e[4], back));
             swept_here = true;
             return 0;
         };
@@ -1788,7 +1851,7 @@ int run_block_main(apples_ctx *ctx, QueryBlock &qb, const Feeder *feed) {
             // clade blocks (build_blocks): the sweep inside whole subtrees of one cluster on a static schedule, cluster-major
             // (sweep_lean.hip: k_blocks_up before the selection's last phase, k_blocks_down + k_blocks_finish after the sweep above
             // them).  With the lean sweep only (MLSE / ME on a big binary tree): its kernels know a block root among the leaves.
-            ctx->blk_active = a.n_blocks > 0 && ctx->params.criterion != APPLES_HYBRID && !pipelined && !ctx->tree.scan && w.small.lean && w.small.lean_leaf && w.big.lean;
+            ctx->blk_active = a.n_blocks > 0 && ctx->params.criterion != APPLES_HYBRID && !ctx->tree.scan && w.small.lean && w.small.lean_leaf && w.big.lean;
             if (ctx->blk_active) {
                 const int64_t n_items = nq * SELECT_CLUSTERS_ACC_CAP + std::min<int64_t>(nq, SELECT_CLUSTERS_BIG_LIST) * a.n_reps;
                 const int64_t n_ints = 3 * n_items + 3 * w.batch + 16 + a.n_reps, n_tiles = n_items / 64 + a.n_reps + 1;
@@ -1917,11 +1980,12 @@ int run_block_main(apples_ctx *ctx, QueryBlock &qb, const Feeder *feed) {
                     });
                 })) return 1;
         } else if (fused) {
-            HIP_TRY(ctx, hipEventRecord(e[0], front));
-            if (fused_counts_format(ctx, qb))  // the matrix-core kernel writes only the non-empty segments' counts
+            if (ovl) HIP_TRY(ctx, hipEventRecord(e[5], back));  // (the distance pass went out on the front stream: ovl_gemm; the selection's timer starts here)
+            else HIP_TRY(ctx, hipEventRecord(e[0], front));
+            if (!ovl && fused_counts_format(ctx, qb))  // the matrix-core kernel writes only the non-empty segments' counts
                 HIP_TRY(ctx, hipMemsetAsync(w.seg_cnt, 0, (size_t)nq * (w.stride / 64) * sizeof(int32_t), front));
-            if (launch_counts_fused(ctx, qb, q0, nh, dist_tile_for(ctx, nq), w.dist, w.seg_slot, w.seg_cnt)) return 1;
-            if (nh < nq) {  // the rest of the chunk travels meanwhile (split_feed: the GEMM form, packed survivors in seg_slot alone)
+            if (!ovl && launch_counts_fused(ctx, qb, q0, nh, dist_tile_for(ctx, nq), w.dist, w.seg_slot, w.seg_cnt)) return 1;
+            if (!ovl && nh < nq) {  // the rest of the chunk travels meanwhile (split_feed: the GEMM form, packed survivors in seg_slot alone)
                 if (feed_rest(i)) return 1;
                 HIP_TRY(ctx, hipStreamWaitEvent(front, ctx->ev_feed[2 * i + 1], 0));
                 if (launch_counts_fused(ctx, qb, q0 + nh, nq - nh, dist_tile_for(ctx, nq), w.dist, w.seg_slot + nh * w.stride,
@@ -1934,8 +1998,10 @@ int run_block_main(apples_ctx *ctx, QueryBlock &qb, const Feeder *feed) {
             const bool exfix = fused_counts_format(ctx, qb) && (a.ex_off != nullptr || ctx->jc_mmax_true != nullptr);
             const bool ex_kernel = knob_on(ctx, "APPLES_EXOTIC_FIX_KERNEL");
             if (exfix && ex_kernel && launch_exotic_fix(ctx, qb, q0, nq, w.seg_slot, w.seg_cnt, w.n_obs)) return 1;
-            HIP_TRY(ctx, hipEventRecord(e[1], front));
-            ++launches;
+            if (!ovl) {
+                HIP_TRY(ctx, hipEventRecord(e[1], front));
+                ++launches;
+            }
             SelectArgs sa = select_args_alignment(ctx, qb, q0);
             sa.seg_lut = fused_counts_format(ctx, qb) ? ctx->jc_lut : nullptr;
             if (exfix && ex_kernel) sa.seg_surv = w.n_obs;  // (k_exotic_fix left the survivor counts where k_select_fast puts the observed counts)
@@ -1976,10 +2042,6 @@ int run_block_main(apples_ctx *ctx, QueryBlock &qb, const Feeder *feed) {
             if (launch_select(ctx, select_args_alignment(ctx, qb, q0), nq)) return 1;
             HIP_TRY(ctx, hipEventRecord(e[2], front));
         }
-        if (pipelined) {
-            HIP_TRY(ctx, hipEventRecord(ctx->ev_front[set], front));
-            HIP_TRY(ctx, hipStreamWaitEvent(back, ctx->ev_front[set], 0));
-        }
         if (feed && feed_rest(i)) return 1;  // (a route that did not ask for the second piece itself: nothing left behind)
         if (!swept_here) {
             HIP_TRY(ctx, hipEventRecord(e[3], back));
@@ -2002,13 +2064,15 @@ int run_block_main(apples_ctx *ctx, QueryBlock &qb, const Feeder *feed) {
             HIP_TRY(ctx, hipEventRecord(e[4], back));
         }
         ctx->blk_active = false;
-        if (pipelined) HIP_TRY(ctx, hipEventRecord(ctx->ev_back[set], back));
-        if (feed && i + 1 < n_sub && feed_chunk(i + 1)) return 1;  // the next chunk travels while this sub-batch's kernels run
+        if (ovl) HIP_TRY(ctx, hipEventRecord(ctx->ev_back[set], back));  // set `set` of seg_slot / seg_cnt is free again
+        // the next chunk travels while this sub-batch's kernels run (overlapped: the one after it -- GEMM(i + 1) is enqueued already)
+        const int64_t nxt = i + (ovl ? 2 : 1);
+        if (feed && nxt < n_sub && feed_chunk(nxt)) return 1;
     }
-    if (pipelined) {
-        HIP_TRY(ctx, hipEventRecord(e_stop, back));
-        HIP_TRY(ctx, hipStreamWaitEvent(front, e_stop, 0));
-        if ((n_sub & 1) == 0) swap_bufs(w);  // leave the host view on set 0
+    if (ovl) {
+        HIP_TRY(ctx, hipEventRecord(ctx->ev_bigfree, back));
+        HIP_TRY(ctx, hipStreamWaitEvent(front, ctx->ev_bigfree, 0));
+        if (seg_view != 0) { std::swap(w.seg_slot, w.seg_slot2); std::swap(w.seg_cnt, w.seg_cnt2); }  // leave the host view on set 0
     }
     int32_t rag[2] = {0, 0};
     if (w.ragged) HIP_TRY(ctx, hipMemcpyAsync(rag, ctx->d_rag, sizeof(rag), hipMemcpyDeviceToHost, front));
@@ -2039,7 +2103,9 @@ int run_block_main(apples_ctx *ctx, QueryBlock &qb, const Feeder *feed) {
             (void)hipEventElapsedTime(&fms, e[0], e[5]);
             ctx->t_ms[APPLES_T_FILTER] += fms;
         }
-        (void)hipEventElapsedTime(&ms, e[1], e[2]); ctx->t_ms[APPLES_T_SELECT] += ms;
+        // (overlapped route: each phase by its own events -- distance on the front stream, selection and sweep on the back stream beside
+        // the next distance pass; the sums add up to more than the total)
+        (void)hipEventElapsedTime(&ms, e[ovl ? 5 : 1], e[2]); ctx->t_ms[APPLES_T_SELECT] += ms;
         (void)hipEventElapsedTime(&ms, e[3], e[4]); ctx->t_ms[APPLES_T_SWEEP] += ms;
     }
     float ms = 0;
@@ -2909,7 +2975,7 @@ int apples_last_timing(const apples_ctx *ctx, double *ms, int32_t n) {
 
 const char *apples_describe(apples_ctx *ctx) {
     hipDeviceProp_t prop;
-    char buf[2560];
+    char buf[3072];
     const char *name = "?";
     int cus = 0;
     if (hipGetDeviceProperties(&prop, ctx->device) == hipSuccess) { name = prop.name; cus = prop.multiProcessorCount; }
@@ -2927,7 +2993,8 @@ const char *apples_describe(apples_ctx *ctx) {
              "\"fused_distance_pass\": \"%s\", \"gemm_split_sites\": %d, \"k_split_launches\": %lld, \"cluster_k_split_launches\": %lld, \"fp4_reference_image_bytes\": %lld, \"sweep_layout\": \"%s\", \"cluster_fused\": %d, "
              "\"scoredist_filter\": %d, \"scoredist_image_bytes\": %lld, \"cluster_blocks\": %d, \"block_items_last_batch\": %d, \"block_tiles_last_batch\": %d, "
              "\"exotic_symbols_as_gaps\": %d, \"exotic_sites_max_per_row\": %d, \"eight_plane_copy\": %d, "
-             "\"ragged_rows\": %d, \"row_small\": %lld, \"big_rows\": %lld, \"big_rows_last_batch\": %d, \"full_rows_for_good\": %d}",
+             "\"ragged_rows\": %d, \"row_small\": %lld, \"big_rows\": %lld, \"big_rows_last_batch\": %d, \"full_rows_for_good\": %d, "
+             "\"overlap\": %d, \"overlap_batches\": %d}",
              name, cus, ctx->tree.n_nodes, ctx->tree.height, ctx->tree.max_children, (long long)a.n_rows, (long long)a.n_refs,
              (long long)a.n_reps, a.L, a.planes, a.all_singleton ? 1 : 0,
              (long long)((int64_t)a.G * (a.planes + 1) * a.slots_pad * 16), (long long)ctx->ws.batch, ctx->ws.small.wgs,
@@ -2957,7 +3024,9 @@ const char *apples_describe(apples_ctx *ctx) {
              // bytes beyond ACGT- (DevAlign::ex_ok): the context keeps them as gaps in its 2-plane rows and fp4 images; the most such
              // sites in one reference row; the 8-plane copy exists (built with the first such byte, in the reference or in a query)
              a.ex_ok ? 1 : 0, (int)a.ex_max, a.packed8 ? 1 : 0,
-             ctx->ws.ragged ? 1 : 0, (long long)ctx->ws.row_small, (long long)ctx->ws.row_big, (int)big_used, ctx->no_ragged ? 1 : 0);
+             ctx->ws.ragged ? 1 : 0, (long long)ctx->ws.row_small, (long long)ctx->ws.row_big, (int)big_used, ctx->no_ragged ? 1 : 0,
+             // the last block's pass: distance GEMM of batch b + 1 beside selection and sweep of batch b (run_block_main); its device batches
+             ctx->overlap, ctx->overlap_batches);
     ctx->desc = buf;
     return ctx->desc.c_str();
 }

@@ -302,7 +302,8 @@ struct Workspace {
     int32_t *overflow_count = nullptr; // [1]
     int32_t *cls_list = nullptr;       // [4][batch] placeable queries by size class, largest class first
     int32_t *cls_count = nullptr;      // [8]: 4 class counts, then 3 dynamic-queue cursors (small / routed / overflow)
-    BatchBuf alt;                      // the other buffer set (swapped in by the pipelined driver)
+    int32_t *seg_slot2 = nullptr, *seg_cnt2 = nullptr;  // the overlapped driver's second set of the two (api.hip: run_block_main)
+    BatchBuf alt;                      // the other buffer set (swapped in by the table route's pipelined driver)
     bool has_alt = false;
 };
 
@@ -335,6 +336,7 @@ struct apples_ctx {
     GemmThreshold gemm_thr;
     int n_cu = 0;  // compute units of the device (dist_gemm.hip's persistent grid)
     int64_t cur_batch_queries = 0;  // queries of the device batch under way (api.hip:route_threshold)
+    int overlap = 0, overlap_batches = 0;  // the last block's pass took the overlapped route (run_block_main); its device batches
     int32_t *jc_mmax = nullptr;  // [L+1] largest mismatch count with 0 <= lut <= threshold, per valid count
     int32_t *jc_mmax_true = nullptr;  // jc_mmax is the FILTER's table where the reference holds bytes beyond ACGT- (a pair's counts may still
                                       // grow by up to ex_max: set_params); this is the rule itself, what k_exotic_fix tests.  nullptr: jc_mmax is
@@ -575,7 +577,8 @@ int launch_expand_queries_f4(apples_ctx *ctx, const uint8_t *d_raw, int64_t n, u
                              hipStream_t st, const int32_t *d_src_row = nullptr, int64_t row0 = 0);
 // dist_gemm.hip
 bool dist_gemm_usable(const apples_ctx *ctx);
-int launch_counts_gemm(apples_ctx *ctx, const QueryBlock &qb, int64_t q0, int64_t nq, int32_t *seg_slot, int32_t *seg_cnt);
+// (share: the form of one four-wavefront workgroup per CU, which leaves half of every CU's registers to a kernel beside it)
+int launch_counts_gemm(apples_ctx *ctx, const QueryBlock &qb, int64_t q0, int64_t nq, int32_t *seg_slot, int32_t *seg_cnt, bool share = false);
 // k_jc69_gemm_long: the fused pass of 2-plane blocks on alignments of GEMM_LONG_MIN_L sites and more; writes k_jc69 MODE 1's format
 bool dist_gemm_long_usable(const apples_ctx *ctx);
 // (image / rows: the reference-side operand image and its padded row count -- DevAlign::ref_f4 and slots_pad by default, the

@@ -39,6 +39,7 @@ typedef float v2f_t __attribute__((ext_vector_type(2)));
 #define GM_AUX 0       // cache policy bits of the DMA loads (experiments: 1 = sc0, 2 = nt)
 #endif
 #define GM_IMG (GM_T * 64)   // bytes of one tile-step image: 256 rows x (t1, t2) x 32 bytes
+#define GM_SHARE_LDS (84 * 1024)  // LDS of a workgroup of the sharing form, padding included: above half of a CU's 160 KB
 
 namespace {
 
@@ -412,12 +413,17 @@ bool dist_gemm_usable(const apples_ctx *ctx) {
     return !(ctx->dbg & APPLES_DBG_NO_DIST_GEMM) && ctx->aln.ref_f4 && ctx->aln.L <= GEMM_MAX_L;
 }
 
-int launch_counts_gemm(apples_ctx *ctx, const QueryBlock &qb, int64_t q0, int64_t nq, int32_t *seg_slot, int32_t *seg_cnt) {
+// `share`: the form that leaves half of every CU to another kernel (api.hip: the overlapped driver runs the selection and the
+// sweep of the batch before beside it).  QT = 128 and ONE four-wavefront workgroup per CU: a wavefront per SIMD, 256 of its 512
+// registers.  The kernel's 72 / 80 KB of LDS would let a CU take two, and a grid of one per CU would then sit two deep on half the
+// chip; dynamic LDS (unused) lifts the workgroup above half a CU's 160 KB, so that the second one cannot land beside the first.
+// Counts and output format are the QT = 256 form's, bit for bit (same decode, same compaction; the tile order differs).
+int launch_counts_gemm(apples_ctx *ctx, const QueryBlock &qb, int64_t q0, int64_t nq, int32_t *seg_slot, int32_t *seg_cnt, bool share) {
     const DevAlign &a = ctx->aln;
     // tuning knob: 128 = two four-wavefront workgroups per CU (measured at C3: 30.8 ms against 29.4 -- what the second
     // workgroup hides of the first one's epilogue and barrier stalls costs more in DMA traffic)
     const int qt_env = (int)knob(ctx, "APPLES_GEMM_QT", 256);
-    const int QT = qt_env == 128 ? 128 : 256;
+    const int QT = (share || qt_env == 128) ? 128 : 256;
     const int TQ = (int)((nq + QT - 1) / QT), TR = (int)(a.slots_pad / GM_T);
     // persistent workgroups: as many as the CUs hold (the kernel's LDS and registers allow 256 / QT per CU), a
     // multiple of the 8 XCDs
@@ -426,15 +432,17 @@ int launch_counts_gemm(apples_ctx *ctx, const QueryBlock &qb, int64_t q0, int64_
         HIP_TRY(ctx, hipGetDeviceProperties(&prop, ctx->device));
         ctx->n_cu = prop.multiProcessorCount;
     }
-    const int cus = (int)knob(ctx, "APPLES_GEMM_CUS", 0);  // experiment: leave CUs to a concurrent sweep
-    const int per_cu = (int)knob(ctx, "APPLES_GEMM_WGS_PER_CU", 0);  // experiment: one four-wavefront workgroup per CU (QT = 128)
-    const int64_t grid = std::max(8, (cus > 0 ? std::min(cus, ctx->n_cu) : ctx->n_cu) / 8 * 8) * (per_cu > 0 ? std::min(per_cu, 256 / QT) : 256 / QT);
+    const int64_t grid = std::max(8, ctx->n_cu / 8 * 8) * (share ? 1 : 256 / QT);
     const bool table = knob_on(ctx, "APPLES_GEMM_TABLE");  // diagnostic knob: threshold through the LDS table
     const bool lin = ctx->gemm_thr.ok && !table;
     const int R = (a.G * 2 - 2) % 3;
-    if (a.L > GEMM_MAX_L13) {  // 2 047 .. 4 092 sites: the validity sum at 2^12, integer decode, the threshold through the table
+    // (static LDS of the QT = 128 forms: three generations of 24 KB, and the table where the threshold goes through it)
+    const bool tab12 = a.L > GEMM_MAX_L13;
+    // (the 2^12 form's 88 KB are above half a CU as they are -- and its registers leave a neighbour nothing: the driver does not share there)
+    const unsigned dyn = share && !tab12 ? GM_SHARE_LDS - (3 * (128 * 64 + GM_IMG) + (lin ? 0 : 2048 * 4)) : 0u;
+    if (tab12) {  // 2 047 .. 4 092 sites: the validity sum at 2^12, integer decode, the threshold through the table
 #define GM_LAUNCH12(R_, QT_)                                                                                         \
-    hipLaunchKernelGGL((k_jc69_gemm<false, R_, QT_, 12>), dim3((unsigned)grid), dim3(QT_ * 2), 0, ctx->stream, a.ref_f4, \
+    hipLaunchKernelGGL((k_jc69_gemm<false, R_, QT_, 12>), dim3((unsigned)grid), dim3(QT_ * 2), dyn, ctx->stream, a.ref_f4, \
                        qb.qf4, q0, a.slots_pad, a.G * 2, nq, a.L, TQ, TR, seg_slot, seg_cnt, ctx->jc_mmax, ctx->gemm_thr)
         if (QT == 256) { if (R == 0) GM_LAUNCH12(0, 256); else if (R == 1) GM_LAUNCH12(1, 256); else GM_LAUNCH12(2, 256); }
         else { if (R == 0) GM_LAUNCH12(0, 128); else if (R == 1) GM_LAUNCH12(1, 128); else GM_LAUNCH12(2, 128); }
@@ -443,7 +451,7 @@ int launch_counts_gemm(apples_ctx *ctx, const QueryBlock &qb, int64_t q0, int64_
         return 0;
     }
 #define GM_LAUNCH(LIN_, R_, QT_)                                                                                     \
-    hipLaunchKernelGGL((k_jc69_gemm<LIN_, R_, QT_>), dim3((unsigned)grid), dim3(QT_ * 2), 0, ctx->stream, a.ref_f4,  \
+    hipLaunchKernelGGL((k_jc69_gemm<LIN_, R_, QT_>), dim3((unsigned)grid), dim3(QT_ * 2), dyn, ctx->stream, a.ref_f4,  \
                        qb.qf4, q0, a.slots_pad, a.G * 2, nq, a.L, TQ, TR, seg_slot, seg_cnt,                         \
                        ctx->jc_mmax, ctx->gemm_thr)
 #define GM_LAUNCH_R(LIN_, QT_)                                                                                       \
