@@ -655,7 +655,11 @@ int setup_alignment(apples_ctx *ctx, const apples_tree *t, const apples_alignmen
         HIP_TRY(ctx, hipMemsetAsync(a.packed, 0, (size_t)words * sizeof(uint4), ctx->stream));
         // bytes beyond ACGT- in a singleton context whose fused pass runs on the matrix cores: the 2-plane rows and the fp4 images
         // keep them as gaps, the 8-plane form comes beside them (DevAlign::ex_ok)
-        a.ex_ok = a.all_singleton && dist_mfma_enabled(ctx) && a.L < 8192;
+        // ... and in a clustered context that takes the fused route by representatives in its short forms (the conditions of the
+        // panels below): the panels keep them as gaps, mask planes beside them say where they are (DevAlign::rep_x / x_rm)
+        const bool cl_ex = !a.all_singleton && a.n_refs <= SELECT_CLUSTERS_MAX_SLOTS && !(ctx->dbg & APPLES_DBG_NO_FUSE);
+        a.ex_ok = (a.all_singleton || cl_ex) && dist_mfma_enabled(ctx) && a.L < 8192;
+        std::vector<int32_t> cl_bad;  // clustered: the flagged slots
         int32_t *d_row_bad = nullptr;
         if (a.ex_ok) {
             if (dev_alloc(ctx, &d_row_bad, a.slots_pad)) return 1;
@@ -682,9 +686,13 @@ int setup_alignment(apples_ctx *ctx, const apples_tree *t, const apples_alignmen
                 off[s + 1] = (int32_t)sites.size();
                 a.ex_max = std::max(a.ex_max, off[s + 1] - off[s]);
             }
-            if (sites.empty()) sites.push_back(0);
-            if (dev_upload(ctx, &a.ex_off, off.data(), (int64_t)off.size())) return 1;
-            if (dev_upload(ctx, &a.ex_site, sites.data(), (int64_t)sites.size())) return 1;
+            if (a.all_singleton) {
+                if (sites.empty()) sites.push_back(0);
+                if (dev_upload(ctx, &a.ex_off, off.data(), (int64_t)off.size())) return 1;
+                if (dev_upload(ctx, &a.ex_site, sites.data(), (int64_t)sites.size())) return 1;
+            } else {
+                cl_bad.swap(bad);  // (the mask planes come with the panels, below; ex_max is what set_params loosens the table by)
+            }
             if (ensure_packed8(ctx)) return 1;
             exotic = 0;
         }
@@ -715,6 +723,34 @@ int setup_alignment(apples_ctx *ctx, const apples_tree *t, const apples_alignmen
         if (!a.all_singleton && a.planes == 2 && a.n_refs <= SELECT_CLUSTERS_MAX_SLOTS && (a.G <= 64 || cl_long) &&
             !(ctx->dbg & APPLES_DBG_NO_FUSE) && dist_mfma_enabled(ctx)) {
             if (launch_build_cluster_panels(ctx)) return 1;
+            if (!cl_bad.empty()) {
+                // bytes beyond ACGT- (the panels hold them as gaps): which clusters and which representatives -- consensus rows can
+                // carry them -- then their mask planes from the caller's rows
+                std::vector<int32_t> xoff((size_t)a.n_reps, -1), rbad((size_t)a.n_reps, 0);
+                int64_t words = 0;
+                bool any_rep = false;
+                a.n_xclusters = 0;
+                for (int64_t j = 0; j < a.n_reps; ++j) {
+                    bool flagged = false;
+                    for (int m = rep_moff[j]; m < rep_moff[j + 1] && !flagged; ++m) flagged = cl_bad[mem_slot[m]] != 0;
+                    if (flagged) {
+                        xoff[j] = (int32_t)words;
+                        words += (int64_t)a.G * (rep_moff[j + 1] - rep_moff[j]);
+                        ++a.n_xclusters;
+                    }
+                    rbad[j] = cl_bad[rep_slot[j]] ? 1 : 0;
+                    any_rep |= rbad[j] != 0;
+                }
+                if (dev_upload(ctx, &a.cl_xoff, xoff.data(), a.n_reps)) return 1;
+                if (dev_alloc(ctx, &a.x_rm, std::max<int64_t>(words, 1))) return 1;
+                if (any_rep) {
+                    if (dev_upload(ctx, &a.rep_bad, rbad.data(), a.n_reps)) return 1;
+                    if (dev_alloc(ctx, &a.rep_x, (int64_t)a.G * a.reps_pad)) return 1;
+                    HIP_TRY(ctx, hipMemsetAsync(a.rep_x, 0, (size_t)a.G * a.reps_pad * sizeof(uint4), ctx->stream));
+                }
+                if (launch_pack_exotic_masks(ctx, a.cl_xoff, a.x_rm, a.rep_x)) return 1;
+                HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (the vectors are locals)
+            }
             if (cl_long) {
                 // the representatives' rows once more as a compact fp4 image in representative order (k_jc69_gemm_long's reference
                 // operand: reps_pad is a multiple of its 256-row tiles, the padding rows are all-gap), through a row map
@@ -1010,20 +1046,25 @@ int ensure_workspace(apples_ctx *ctx, int64_t members, int64_t stride, int64_t w
         per_q += seg2_per_q;
         batch = size_batch();
     }
+    const bool w_ragged = w.row_off != nullptr;  // the rows as they were allocated
     bool regrow = batch > w.batch || members > w.obs_cap || stride > w.stride || (need_counts && !w.counts) ||
                   (need_xe && !w.big.xe) || (need_dist && !w.dist) || (need_fused && !w.seg_slot) || (need_alt && !w.has_alt) || (seg2 && !w.seg_slot2) ||
                   // full rows wanted where only a slice exists (run_block steps by w.batch) -- unless the whole block fits the slice
                   // (a slim workspace serves the few queries of an exact8 block as it is: no regrowing back and forth)
                   (!slim && !cslim && w.dist_rows < std::min(w.batch, round_up(std::max<int64_t>(want_batch, 1), 32))) ||
-                  // rows of another shape (every other route indexes q x obs_cap / q x stride)
-                  ragged != w.ragged || (ragged && (row_small != w.row_small || row_big > w.row_big));
-    if (!regrow) return 0;
+                  // rows of another shape (every other route indexes q x obs_cap / q x stride) -- unless a block of plain full rows
+                  // fits the ragged rows' buffers as they are (dist_rows whole rows of dist, obs_node and obs_dist: the ex_block behind a
+                  // clustered pass); it then reads them as q x obs_cap / q x stride (w.ragged: how this block reads them) and the next
+                  // clustered block goes back to the ragged form, nothing freed either way
+                  (ragged && (!w_ragged || row_small != w.row_small || row_big > w.row_big)) ||
+                  (!ragged && w_ragged && (slim || cslim || need_fused));
+    if (!regrow) { w.ragged = ragged; return 0; }
     if (!ctx->blk_cache.empty()) {  // cached block buffers count as used in hipMemGetInfo: give them back, then size the batch
         for (auto &c : ctx->blk_cache) dev_free(c.second);
         ctx->blk_cache.clear();
         batch = size_batch();
     }
-    if ((slim == w.slim || !w.slim) && (cslim == w.cslim || !w.cslim) && ragged == w.ragged) batch = std::max(batch, w.batch);
+    if ((slim == w.slim || !w.slim) && (cslim == w.cslim || !w.cslim) && ragged == w_ragged) batch = std::max(batch, w.batch);
     if (!slim) batch = std::min(batch, std::max<int64_t>(capq, 32));  // (a slim workspace's batch would not fit with full rows)
     batch = round_up(std::max<int64_t>(batch, 1), 32);
     const int64_t drows = (slim || cslim) ? std::min(batch, std::max<int64_t>(2048, batch / 8)) : batch;
@@ -1560,6 +1601,7 @@ int run_ex_block(apples_ctx *ctx, QueryBlock &qb) {
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     for (int i = 0; i < APPLES_T_COUNT; ++i) ctx->t_ms[i] += t0[i];
+    ctx->ws.ragged = ctx->ws.row_off != nullptr;  // (ensure_workspace: the main pass's rows, read as plain ones for x)
     return 0;
 }
 
@@ -1811,6 +1853,13 @@ int run_block_main(apples_ctx *ctx, QueryBlock &qb, const Feeder *feed) {
             // the member distances of accepted clusters on the matrix cores (k_cluster_dist_mfma) unless APPLES_DBG_NO_CLUSTER_MFMA
             sa.cl_mfma = (!csd && !(ctx->dbg & APPLES_DBG_NO_CLUSTER_MFMA)) ? 1 : 0;
             sa.overlap = ctx->params.overlap_frac; sa.rep_stride = a.reps_pad; sa.tmp_d = w.dist;
+            if (!csd && !cl_long && a.cl_xoff) {  // panels with bytes beyond ACGT- held as gaps: the mask planes, and the rule's own table
+                sa.rep_x = a.rep_x; sa.rep_bad = a.rep_bad; sa.x_rm = a.x_rm; sa.cl_xoff = a.cl_xoff;
+                if (a.rep_x || ctx->jc_mmax_true) {  // (the representatives' survivors are a superset: k_cluster_rep_fix)
+                    sa.ex_mmax = ctx->jc_mmax_true ? ctx->jc_mmax_true : ctx->jc_mmax;
+                    sa.ex_all = ctx->jc_mmax_true ? 1 : 0;
+                }
+            }
             sa.slow_hint = w.slow_list + w.batch;
             sa.lvl_slots = a.lvl_slots;
             {   // scratch of the cluster-major distance pass: per-cluster counters, the (query, offset) lists, the tile table
@@ -2409,6 +2458,7 @@ void apples_ctx_destroy(apples_ctx *ctx) {
     DevAlign &a = ctx->aln;
     dev_free(a.raw); dev_free(a.d_slot_row); dev_free(a.packed); dev_free(a.ref_f4); dev_free(a.rep_f4); dev_free(a.rep_boff); dev_free(a.rep_loff); dev_free(a.loose_mp); dev_free(a.blk_rec_i); dev_free(a.blk_rec_e); dev_free(a.blk_rec_c); dev_free(a.blk_rec_p); dev_free(a.blk_pk_i); dev_free(a.blk_pk_e); dev_free(a.blk_stat[0]); dev_free(a.blk_stat[1]); dev_free(a.rep_soff); dev_free(a.cl_order); dev_free(a.mem_block); dev_free(a.blk_root); dev_free(a.blk_rslot); dev_free(a.blk_nodes); dev_free(a.e_of_slot); dev_free(a.e_of_blk); dev_free(a.e_node); dev_free(a.lvl_e); dev_free(a.rep_packed); dev_free(a.packed_rm); dev_free(a.aa_rep_idx); dev_free(a.aa_rep_mask); dev_free(a.aa_cm_idx); dev_free(a.aa_cm_mask); dev_free(a.aa_idx); dev_free(a.aa_mask); dev_free(a.sd_ref4); dev_free(a.sd_nvr); dev_free(a.aa_rows); dev_free(a.aa_mrows); dev_free(ctx->sd_tq4); dev_free(ctx->sd_list_img); dev_free(ctx->sd_list_ints); dev_free(a.slot_node); dev_free(a.slot_level); dev_free(a.lvl_slots);
     dev_free(a.slot_rep); dev_free(a.slot_mpos); dev_free(a.rep_slot); dev_free(a.rep_moff); dev_free(a.mem_slot);
+    dev_free(a.rep_x); dev_free(a.rep_bad); dev_free(a.x_rm); dev_free(a.cl_xoff);
     dev_free(ctx->jc_lut); dev_free(ctx->jc_mmax); dev_free(ctx->jc_mmax_true); dev_free(ctx->jc_bound_long); dev_free(ctx->blosum); dev_free(ctx->d_col_perm); dev_free(ctx->d_col_node);
     dev_free(ctx->d_col_level);
     for (int i = 0; i < 8; ++i)
@@ -2992,7 +3042,7 @@ const char *apples_describe(apples_ctx *ctx) {
              "\"packed_bytes\": %lld, \"batch\": %lld, \"sweep_workgroups\": %d, \"sweep_team_cap\": %lld, \"sweep_big_workgroups\": %d, \"jc_lut\": %d, \"sweep\": \"%s\", "
              "\"fused_distance_pass\": \"%s\", \"gemm_split_sites\": %d, \"k_split_launches\": %lld, \"cluster_k_split_launches\": %lld, \"fp4_reference_image_bytes\": %lld, \"sweep_layout\": \"%s\", \"cluster_fused\": %d, "
              "\"scoredist_filter\": %d, \"scoredist_image_bytes\": %lld, \"cluster_blocks\": %d, \"block_items_last_batch\": %d, \"block_tiles_last_batch\": %d, "
-             "\"exotic_symbols_as_gaps\": %d, \"exotic_sites_max_per_row\": %d, \"eight_plane_copy\": %d, "
+             "\"exotic_symbols_as_gaps\": %d, \"exotic_sites_max_per_row\": %d, \"eight_plane_copy\": %d, \"cluster_exotic_clusters\": %d, "
              "\"ragged_rows\": %d, \"row_small\": %lld, \"big_rows\": %lld, \"big_rows_last_batch\": %d, \"full_rows_for_good\": %d, "
              "\"overlap\": %d, \"overlap_batches\": %d}",
              name, cus, ctx->tree.n_nodes, ctx->tree.height, ctx->tree.max_children, (long long)a.n_rows, (long long)a.n_refs,
@@ -3023,7 +3073,8 @@ const char *apples_describe(apples_ctx *ctx) {
              (int)a.n_blocks, (int)blk_cnt[0], (int)blk_cnt[2],
              // bytes beyond ACGT- (DevAlign::ex_ok): the context keeps them as gaps in its 2-plane rows and fp4 images; the most such
              // sites in one reference row; the 8-plane copy exists (built with the first such byte, in the reference or in a query)
-             a.ex_ok ? 1 : 0, (int)a.ex_max, a.packed8 ? 1 : 0,
+             // (a clustered context: the clusters with a member that holds one -- their tiles take k_cluster_dist_mfma's EX form)
+             a.ex_ok ? 1 : 0, (int)a.ex_max, a.packed8 ? 1 : 0, (int)a.n_xclusters,
              ctx->ws.ragged ? 1 : 0, (long long)ctx->ws.row_small, (long long)ctx->ws.row_big, (int)big_used, ctx->no_ragged ? 1 : 0,
              // the last block's pass: distance GEMM of batch b + 1 beside selection and sweep of batch b (run_block_main); its device batches
              ctx->overlap, ctx->overlap_batches);

@@ -135,7 +135,8 @@ struct DevAlign {
     //     top-up pass, apples_distances, the unfused route) and for query blocks that carry such bytes themselves (QueryBlock::exact8);
     //   * ex_off / ex_site: per slot the sites that hold such a byte -- k_exotic_fix adds them back to the counts of the fused
     //     pass's survivors (a site where the row has such a byte and the query a letter is valid and a mismatch).
-    bool ex_ok = false;           // the context takes this route (singleton clusters, JC69, matrix-core passes enabled, L < 8192)
+    bool ex_ok = false;           // the context takes this route (JC69, matrix-core passes enabled, L < 8192; singleton clusters, or a
+                                  // clustered context on the fused route by representatives: rep_x / x_rm below in place of ex_off / ex_site)
     uint4 *packed8 = nullptr;     // [G][9][slots_pad]; built with the first such byte, in the reference or in a query block
     int32_t *ex_off = nullptr;    // [n_rows + 1] CSR over slots, or nullptr: the reference rows hold no such byte
     uint16_t *ex_site = nullptr;  // [ex_off[n_rows]] sites, ascending per slot
@@ -144,6 +145,13 @@ struct DevAlign {
     uint4 *packed_rm = nullptr;   // the member rows cluster by cluster, interleaved per plane word (dist.hip:k_cluster_major): [n_refs * G*3]
     uint4 *rep_packed = nullptr;  // [G][3][reps_pad] the representatives' rows, in representative order
     int64_t reps_pad = 0;
+    // ... bytes beyond ACGT- on that route (ex_ok; the panels hold them as gaps): one mask plane per row, bit = the site holds such a
+    // byte (pack.hip: k_pack_exotic_masks).  k = popc(mask & the query's gap plane) goes into both counts of a pair.
+    uint4 *rep_x = nullptr;       // [G][reps_pad] the representatives'; nullptr: no representative holds such a byte
+    int32_t *rep_bad = nullptr;   // [n_reps] 1: the representative holds one (with rep_x)
+    uint4 *x_rm = nullptr;        // the members' of the flagged clusters: cl_xoff[c] + g * size(c) + position
+    int32_t *cl_xoff = nullptr;   // [n_reps] first word of the cluster's masks in x_rm, -1: no member holds such a byte; nullptr: no cluster
+    int32_t n_xclusters = 0;      // flagged clusters
     uint8_t *rep_f4 = nullptr;    // alignments of GEMM_LONG_MIN_L sites and more: the representatives' rows in representative order as a compact fp4
                                   // operand image ([reps_pad][2G] blocks in ref_f4's tiled form; padding rows all-gap) -- k_jc69_gemm_long reads it
     // ... and of scoredist contexts (the default route of -p): the representatives' rows in representative order, in the layout
@@ -263,6 +271,8 @@ struct Workspace {
     // phase 2), or that leaves the fast phases (phase 4, k_select), takes one of `row_big` rows of `stride` entries behind them, handed
     // out by a cursor (cls_count[22]); row_off[q] = where query q's rows start, in entries.  When the big rows run out the queries share
     // the last one (garbage, in bounds), cls_count[23] is raised and run_block repeats the block with full rows for good (ctx->no_ragged).
+    // `ragged` says how the current block reads the rows; allocated ragged = row_off != nullptr (a small block of plain full rows, the
+    // ex_block of a clustered pass, reads the same buffers as q x obs_cap / q x stride: ensure_workspace).
     bool ragged = false;
     int64_t row_small = 0, row_big = 0;
     int64_t *row_off = nullptr;   // [batch]
@@ -415,6 +425,8 @@ int launch_pack_rows(apples_ctx *ctx, const uint8_t *d_raw, int64_t n_rows, int 
                      const int32_t *d_src_row = nullptr, int32_t *d_row_bad = nullptr);
 int launch_pack_aa(apples_ctx *ctx, const uint8_t *d_raw, int64_t n_rows, int L, uint8_t *d_out, uint16_t *d_mask,
                    int64_t slots_pad, bool query_layout, hipStream_t st = nullptr, const int32_t *d_src_row = nullptr);
+// the mask panels of a clustered context with bytes beyond ACGT- (DevAlign::rep_x / x_rm), from a.raw; d_rep_x may be nullptr
+int launch_pack_exotic_masks(apples_ctx *ctx, const int32_t *d_cl_xoff, uint4 *d_x_rm, uint4 *d_rep_x);
 // dist.hip
 int launch_counts(apples_ctx *ctx, const QueryBlock &qb, int64_t q0, int64_t nq, int tile, double *d_dist,
                   uint32_t *d_counts);
@@ -511,6 +523,10 @@ struct SelectArgs {
     // clustered fast path (k_select_clusters): survivors among the representatives come in seg_slot/seg_cnt with
     // row stride rep_stride; member rows are read row-major, the query's words from its packed tile
     const uint4 *packed_rm; const uint4 *qpacked; int G; int L; double overlap; int64_t rep_stride;
+    // ... bytes beyond ACGT- in the panels' rows (DevAlign::rep_x ...; all nullptr in a context without): every member distance of a
+    // flagged cluster counts k, and the representatives' survivors are counted and tested again before phase 1 reads them
+    // (k_cluster_rep_fix, with ex_mmax / ex_all above)
+    const uint4 *rep_x, *x_rm; const int32_t *rep_bad, *cl_xoff;
     int cl_mfma;                        // the member distances of accepted clusters on the matrix cores (k_cluster_dist_mfma), not by bit counts (k_cluster_dist)
     double *tmp_d;            // [nq][stride] member distances before the ordered emission
     int flat_pref;            // k_select_fast: the segment counts' prefix fits LDS (set by the launcher)

@@ -173,6 +173,58 @@ int launch_pack_rows(apples_ctx *ctx, const uint8_t *d_raw, int64_t n_rows, int 
     return 0;
 }
 
+// Clustered JC69 contexts that keep bytes beyond ACGT- as gaps (DevAlign::ex_ok): where those bytes are, as one mask plane per
+// row beside the two panels of dist.hip:launch_build_cluster_panels -- bit = the site holds such a byte.  A pair's counts are
+// (valid + k, mism + k) with k = popc(row's mask & query's gap plane) summed over the words (select.hip).
+//   rep_x : [g][reps_pad]                      the representatives, rep_packed's order (nullptr: no representative holds one)
+//   x_rm  : cl_xoff[c] + g * size(c) + position the members of the flagged clusters, packed_rm's interleaving (cl_xoff[c] < 0: clean)
+// Lanes along the sites as in k_pack_rows_w: a thread = one 32-site word, the four threads of a word group hand theirs to the first.
+// Item i < n_mem is member i of the stored order, the items behind are the representatives.
+__global__ __launch_bounds__(APPLES_TPB) void k_pack_exotic_masks(const uint8_t *__restrict__ raw, int L, int G, const int32_t *__restrict__ slot_row,
+                                                                  int64_t n_mem, const int32_t *__restrict__ mem_slot,
+                                                                  const int32_t *__restrict__ slot_rep, const int32_t *__restrict__ rep_moff,
+                                                                  const int32_t *__restrict__ cl_xoff, uint4 *__restrict__ x_rm,
+                                                                  int64_t n_reps, const int32_t *__restrict__ rep_slot, int64_t reps_pad,
+                                                                  uint4 *__restrict__ rep_x) {
+    const int64_t idx = (int64_t)blockIdx.x * APPLES_TPB + threadIdx.x;
+    const int W4 = G * 4;
+    const int64_t item = idx / W4;
+    const int w = (int)(idx - item * W4);
+    uint4 *dst = nullptr;  // where the item's word group goes (nullptr: nowhere -- a clean cluster, no panel, beyond the items)
+    int slot = 0;
+    if (item < n_mem) {
+        slot = mem_slot[item];
+        const int c = slot_rep[slot];
+        const int64_t b = rep_moff[c], sz = rep_moff[c + 1] - b;
+        if (cl_xoff[c] >= 0 && item >= b && item - b < sz) dst =x_rm + cl_xoff[c] + (int64_t)(w >> 2) * sz + (item - b);
+    } else if (item < n_mem + n_reps && rep_x) {
+        slot = rep_slot[item - n_mem];
+        dst = rep_x + (int64_t)(w >> 2) * reps_pad + (item - n_mem);
+    }
+    uint32_t x = 0;
+    if (dst && w * 32 < L) {
+        const uint8_t *src = raw + (int64_t)slot_row[slot] * L + w * 32;
+        const int nb = min(32, L - w * 32);
+        for (int i = 0; i < nb; ++i) {
+            const uint32_t b = src[i];
+            x |= (uint32_t)!(b == '-' || b == 'A' || b == 'C' || b == 'G' || b == 'T') << i;
+        }
+    }
+    const uint4 px = make_uint4(x, __shfl_down(x, 1, 64), __shfl_down(x, 2, 64), __shfl_down(x, 3, 64));
+    if (dst && (w & 3) == 0) *dst = px;
+}
+
+int launch_pack_exotic_masks(apples_ctx *ctx, const int32_t *d_cl_xoff, uint4 *d_x_rm, uint4 *d_rep_x) {
+    const DevAlign &a = ctx->aln;
+    const int64_t total = (a.n_refs + a.n_reps) * (int64_t)a.G * 4;
+    if (total == 0) return 0;
+    hipLaunchKernelGGL(k_pack_exotic_masks, dim3((unsigned)((total + APPLES_TPB - 1) / APPLES_TPB)), dim3(APPLES_TPB), 0, ctx->stream,
+                       a.raw, a.L, a.G, a.d_slot_row, a.n_refs, a.mem_slot, a.slot_rep, a.rep_moff, d_cl_xoff, d_x_rm, a.n_reps,
+                       a.rep_slot, a.reps_pad, d_rep_x);
+    HIP_TRY(ctx, hipGetLastError());
+    return 0;
+}
+
 // scoredist layout: residue index per site, a2i of apples/distance.py:418-678 (ARNDCQEGHILKMFPSTWYV
 // both cases -> 0..19, every other byte -> 0) with '-' -> 20 (a zero row/column of the table, so
 // gapped sites add +0.0 exactly as nondash*BLOSUM45[...] does at distance.py:706).

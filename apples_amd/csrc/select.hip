@@ -819,7 +819,9 @@ __global__ __launch_bounds__(TPB) void k_select_clusters(SelectArgs a) {
     // a member's (or representative's) distance from its words: word (g, plane) at base[(g * 3 + plane) * stride] -- the
     // cluster-major panel with the cluster's size as stride (the lanes holding consecutive members read consecutive 16
     // bytes), or the representative panel with its padded length
-    auto by_query = [&](const uint4 *row, int64_t sz) -> double {
+    // (xrow: the row's mask plane of bytes beyond ACGT-, word g at xrow[g * sz], or nullptr -- such a site under a letter of the
+    // query is one more valid site and one more mismatch; short forms only)
+    auto by_query = [&](const uint4 *row, int64_t sz, const uint4 *xrow) -> double {
         uint32_t nv = 0, nmis = 0;
         int g = 0;
         if (LONG) {
@@ -861,8 +863,19 @@ __global__ __launch_bounds__(TPB) void k_select_clusters(SelectArgs a) {
         for (; g < G; ++g)
             cluster_count(row[(int64_t)(g * 3) * sz], row[(int64_t)(g * 3 + 1) * sz], row[(int64_t)(g * 3 + 2) * sz], sh_q[g * 3],
                           sh_q[g * 3 + 1], sh_q[g * 3 + 2], nv, nmis);
+        if (xrow) {
+            uint32_t k = 0;
+            for (g = 0; g < G; ++g) {
+                const uint4 x = xrow[(int64_t)g * sz], m = sh_q[g * 3];
+                k += __popc(x.x & m.x) + __popc(x.y & m.y) + __popc(x.z & m.z) + __popc(x.w & m.w);
+            }
+            nv += k; nmis += k;
+        }
         return a.seg_lut[(int64_t)nv * (nv + 1) / 2 + nmis];
     };
+    // a member's mask plane: cluster c, position mp (nullptr: the cluster is clean) / a representative's
+    auto xmem = [&](int c, int mp) -> const uint4 * { return (!LONG && a.cl_xoff && a.cl_xoff[c] >= 0) ? a.x_rm + a.cl_xoff[c] + mp : nullptr; };
+    auto xrep = [&](int64_t j) -> const uint4 * { return (!LONG && a.rep_x && a.rep_bad[j]) ? a.rep_x + j : nullptr; };
     // ---- accepted representatives: the survivors of the representative pass, in representative order
     const int64_t n_seg = a.rep_stride >> 6;
     const int32_t *cnt = a.seg_cnt + q * n_seg;
@@ -876,7 +889,7 @@ __global__ __launch_bounds__(TPB) void k_select_clusters(SelectArgs a) {
         for (int64_t j0 = 0; j0 < a.n_reps; j0 += TPB) {
             const int64_t j = j0 + tid;
             // (scoredist: the full rows of the representative pass hold them)
-            const double d = j < a.n_reps ? (sd ? a.rep_dist[q * a.rep_stride + j] : by_query(a.rep_panel + j, a.rep_stride)) : -1.0;
+            const double d = j < a.n_reps ? (sd ? a.rep_dist[q * a.rep_stride + j] : by_query(a.rep_panel + j, a.rep_stride, xrep(j))) : -1.0;
             if (j < a.n_reps) reprow[j] = d;
             const int in = j < a.n_reps && d >= 0 && d <= a.thr;
             int tot;
@@ -1110,7 +1123,7 @@ __global__ __launch_bounds__(TPB) void k_select_clusters(SelectArgs a) {
                 if (sh_off[mid] <= m) lo = mid; else hi = mid;
             }
             const double d = sd ? sd_dist(a.mem_slot[sh_mb[lo] + (m - sh_off[lo])])
-                                : by_query(a.packed_rm + (int64_t)sh_mb[lo] * (G * 3) + (m - sh_off[lo]), sh_off[lo + 1] - sh_off[lo]);
+                                : by_query(a.packed_rm + (int64_t)sh_mb[lo] * (G * 3) + (m - sh_off[lo]), sh_off[lo + 1] - sh_off[lo], xmem(sh_rep[lo], m - sh_off[lo]));
             tmp[m] = d;
             c += !(d < 0);
         }
@@ -1134,7 +1147,7 @@ __global__ __launch_bounds__(TPB) void k_select_clusters(SelectArgs a) {
             if (tid == 0) { sh_rep[n_acc_all] = bi; sh_mb[n_acc_all] = mb0; sh_off[n_acc_all + 1] = M + sz; }
             c = 0;
             for (int mp = tid; mp < sz; mp += TPB) {
-                const double d = sd ? sd_dist(a.mem_slot[mb0 + mp]) : by_query(a.packed_rm + (int64_t)mb0 * (G * 3) + mp, sz);
+                const double d = sd ? sd_dist(a.mem_slot[mb0 + mp]) : by_query(a.packed_rm + (int64_t)mb0 * (G * 3) + mp, sz, xmem(bi, mp));
                 tmp[M + mp] = d;
                 c += !(d < 0);
             }
@@ -1175,7 +1188,7 @@ __global__ __launch_bounds__(TPB) void k_select_clusters(SelectArgs a) {
                 if (mbk_[e] >= 0) { d_[e] = 1.0; continue; }
                 slot_[e] = a.mem_slot[mb + mp];  // (on its way with the member's distance / words below: neither waits for the other)
                 if (PHASE >= 3) d_[e] = tmp[m];  // k_cluster_dist (phase 4: the block above) left it there
-                else d_[e] = by_query(a.packed_rm + (int64_t)mb * (G * 3) + mp, sh_off[lo + 1] - sh_off[lo]);
+                else d_[e] = by_query(a.packed_rm + (int64_t)mb * (G * 3) + mp, sh_off[lo + 1] - sh_off[lo], xmem(sh_rep[lo], mp));
             }
         }
 #pragma unroll
@@ -1444,6 +1457,10 @@ __global__ __launch_bounds__(APPLES_TPB) void k_cluster_dist(SelectArgs a) {
 #pragma unroll
             for (int k = 0; k < 16; ++k) { nv[k] = 0; nmis[k] = 0; }
             const uint4 *row = a.packed_rm + (int64_t)mb * (G * 3) + mc0 + ml;
+            // a cluster with bytes beyond ACGT- among its members (workgroup-uniform): one more word per group, the member's mask
+            // plane of such sites -- under a letter of the query each is one more valid site and one more mismatch
+            const int xo = (!LONG && a.cl_xoff) ? a.cl_xoff[c] : -1;
+            const uint4 *xrow = xo >= 0 ? a.x_rm + xo + mc0 + ml : nullptr;
             for (int g0 = 0; g0 < G; g0 += CL_GC) {
                 __syncthreads();  // the list above is written / the previous chunk's words are read
                 for (int i = tid; i < nqt * (CL_GC * 3); i += APPLES_TPB) {
@@ -1457,6 +1474,11 @@ __global__ __launch_bounds__(APPLES_TPB) void k_cluster_dist(SelectArgs a) {
                     for (int w = 0; w < CL_GC * 3; ++w)
                         mw[w] = g0 + w / 3 < G ? row[(int64_t)((g0 + w / 3) * 3 + w % 3) * sz] : make_uint4(0, 0, 0, 0);
                 }
+                uint4 xw[CL_GC];
+                if (active && xo >= 0) {
+#pragma unroll
+                    for (int gg = 0; gg < CL_GC; ++gg) xw[gg] = g0 + gg < G ? xrow[(int64_t)(g0 + gg) * sz] : make_uint4(0, 0, 0, 0);
+                }
                 __syncthreads();
                 if (active) {
 #pragma unroll
@@ -1467,6 +1489,15 @@ __global__ __launch_bounds__(APPLES_TPB) void k_cluster_dist(SelectArgs a) {
                             for (int gg = 0; gg < CL_GC; ++gg)
                                 cluster_count(mw[gg * 3], mw[gg * 3 + 1], mw[gg * 3 + 2], sh_qw[j][gg * 3], sh_qw[j][gg * 3 + 1],
                                               sh_qw[j][gg * 3 + 2], nv[k], nmis[k]);
+                            if (xo >= 0) {
+                                uint32_t kx = 0;
+#pragma unroll
+                                for (int gg = 0; gg < CL_GC; ++gg) {
+                                    const uint4 qm = sh_qw[j][gg * 3];
+                                    kx += __popc(xw[gg].x & qm.x) + __popc(xw[gg].y & qm.y) + __popc(xw[gg].z & qm.z) + __popc(xw[gg].w & qm.w);
+                                }
+                                nv[k] += kx; nmis[k] += kx;
+                            }
                         }
                     }
                 }
@@ -1512,8 +1543,19 @@ __global__ __launch_bounds__(APPLES_TPB) void k_cluster_dist(SelectArgs a) {
 // wavefronts per SIMD (80 bytes of scratch per lane at CLM_WAVES = 2, where the short form has 28): the long form is compiled for ONE
 // wavefront per SIMD and uses no scratch ("Clustered route, long forms", has the resource report; the alternative, a second kernel over
 // parked counts, was not built).
-template <bool LONG>
-__global__ __launch_bounds__(WAVE, LONG ? 1 : CLM_WAVES) void k_cluster_dist_mfma(SelectArgs a) {
+// EX (short form, clusters with bytes beyond ACGT- among their members: SelectArgs::cl_xoff): the panel holds those bytes as gaps; a
+// third image, Xm, is expanded from the members' mask plane of such sites (x_rm; fp4 1.0 where the bit is set, same piece-major form,
+// one component) and a fifth MFMA per 32 x 32 block and 64-site block multiplies it with the queries' validity fragment, which is in
+// registers anyway, into a third accumulator set: k = the member's such sites under a letter of the query, each one more valid site
+// and one more mismatch (integers, exact in f32).  The look-up is lut[(valid + k)(valid + k + 1) / 2 + mism + k].  Two launches
+// share the tile table: EX = false is the code as it was and passes over the flagged clusters' tiles, EX = true takes only those
+// (wavefront-uniform per tile).  192 accumulators: compiled for CLM_EX_WAVES wavefronts per SIMD.
+#ifndef CLM_EX_WAVES
+#define CLM_EX_WAVES 1
+#endif
+template <bool LONG, bool EX = false>
+__global__ __launch_bounds__(WAVE, LONG ? 1 : (EX ? CLM_EX_WAVES : CLM_WAVES)) void k_cluster_dist_mfma(SelectArgs a) {
+    static_assert(!(LONG && EX), "the mask planes exist on the short route only");
     // the images of one 64-site block, piece-major: piece (component c, quarter k) of row r -- 8 bytes, 16 sites -- at [c * 4 + k][r].  A lane
     // expands its own row (it holds the row's plane words), so a store instruction writes 64 consecutive pieces and a fragment read
     // 32 consecutive ones: no bank conflicts either way (row-major images as in k_jc69_mfma cost this kernel four-way conflicts on
@@ -1522,6 +1564,7 @@ __global__ __launch_bounds__(WAVE, LONG ? 1 : CLM_WAVES) void k_cluster_dist_mfm
     // bits cleared -- two bit operations per fragment register (as dist_gemm.hip), half the LDS traffic, which is what bounds the loop
     __shared__ uint2 Aq[8][64];  // the tile's queries
     __shared__ uint2 Bm[8][64];  // 64 members
+    __shared__ uint2 Xm[EX ? 4 : 1][64];  // EX: the members' sites with a byte beyond ACGT-
     __shared__ int sh_q[64], sh_o[64], sh_self[64];
     const int lane = threadIdx.x;
     const int G = a.G;
@@ -1542,6 +1585,7 @@ __global__ __launch_bounds__(WAVE, LONG ? 1 : CLM_WAVES) void k_cluster_dist_mfm
         const int4 tile = a.cl_tiles[t];
         const int c = tile.x, nqt = tile.z;
         const int mb = a.rep_moff[c], sz = a.rep_moff[c + 1] - mb;
+        if (!LONG && a.cl_xoff && (a.cl_xoff[c] >= 0) != EX) continue;  // (the other launch's tile)
         __builtin_amdgcn_wave_barrier();  // (the previous tile's readers of sh_q / sh_o)
         {
             const int2 it = a.cl_items[tile.y + (lane < nqt ? lane : 0)];
@@ -1557,19 +1601,21 @@ __global__ __launch_bounds__(WAVE, LONG ? 1 : CLM_WAVES) void k_cluster_dist_mfm
             const bool mj1 = msz > 32;
             const int ml = lane < msz ? lane : msz - 1;  // (lanes beyond the chunk repeat its last member: computed, not written)
             const uint4 *rsrc = a.packed_rm + (int64_t)mb * (G * 3) + mc0 + ml;
-            v16f_t s1[2][2], s2[2][2];
+            const uint4 *xsrc = EX ? a.x_rm + a.cl_xoff[c] + mc0 + ml : nullptr;  // group g at g * sz beyond this
+            v16f_t s1[2][2], s2[2][2], s3[EX ? 2 : 1][EX ? 2 : 1];
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
                 for (int j = 0; j < 2; ++j)
 #pragma unroll
-                    for (int x = 0; x < 16; ++x) { s1[i][j][x] = 0.f; s2[i][j][x] = 0.f; }
-            uint4 qm, q0, q1, pm, p0, p1;
+                    for (int x = 0; x < 16; ++x) { s1[i][j][x] = 0.f; s2[i][j][x] = 0.f; if (EX) s3[i][j][x] = 0.f; }
+            uint4 qm, q0, q1, pm, p0, p1, px;
             auto fetch = [&](int g, uint4 &am, uint4 &a0, uint4 &a1, uint4 &bm, uint4 &b0, uint4 &b1) {
                 const uint4 *qp = qsrc + (int64_t)g * 48;
                 am = qp[0]; a0 = qp[1]; a1 = qp[2];
                 const uint4 *rp = rsrc + (int64_t)(g * 3) * sz;
                 bm = rp[0]; b0 = rp[sz]; b1 = rp[2 * (int64_t)sz];
+                if (EX) px = xsrc[(int64_t)g * sz];
             };
             fetch(0, qm, q0, q1, pm, p0, p1);
             for (int g = 0; g < G; ++g) {
@@ -1580,9 +1626,25 @@ __global__ __launch_bounds__(WAVE, LONG ? 1 : CLM_WAVES) void k_cluster_dist_mfm
                     expand_row(Aq, y ? qm.w : qm.y, y ? q0.w : q0.y, y ? q1.w : q1.y, 1);
                     expand_row(Bm, y ? pm.z : pm.x, y ? p0.z : p0.x, y ? p1.z : p1.x, 0);
                     expand_row(Bm, y ? pm.w : pm.y, y ? p0.w : p0.y, y ? p1.w : p1.y, 1);
+                    if (EX) {
+#pragma unroll
+                        for (int h = 0; h < 2; ++h) {  // (expand_row's validity nibbles alone, of the mask word)
+                            const uint32_t xw = y ? (h ? px.w : px.z) : (h ? px.y : px.x);
+#pragma unroll
+                            for (int k = 0; k < 2; ++k) Xm[2 * h + k][lane] = make_uint2(((xw >> (2 * k)) << 1) & 0x22222222u, (xw >> (2 * k)) & 0x22222222u);
+                        }
+                    }
                     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
                     {
                         v4i_t fa[2][2], fb[2][2];  // [t1 | t2][row block]
+                        v4i_t fx[2];
+                        if (EX) {
+#pragma unroll
+                            for (int j = 0; j < 2; ++j) {
+                                const uint2 x0 = Xm[2 * fh][j * 32 + fr], x1 = Xm[2 * fh + 1][j * 32 + fr];
+                                fx[j] = v4i_t{(int)x0.x, (int)x0.y, (int)x1.x, (int)x1.y};
+                            }
+                        }
 #pragma unroll
                         for (int cc = 0; cc < 2; ++cc)
 #pragma unroll
@@ -1617,6 +1679,7 @@ __global__ __launch_bounds__(WAVE, LONG ? 1 : CLM_WAVES) void k_cluster_dist_mfm
                                     if ((i == 1 && !qi1) || (j == 1 && !mj1)) continue;  // (wave-uniform)
                                     if (cc < 3) s1[i][j] = mfma_f4(fa[set][i], fb[set][j], s1[i][j]);
                                     else s2[i][j] = mfma_f4(fa[set][i], fb[set][j], s2[i][j]);
+                                    if (EX && cc == 3) s3[i][j] = mfma_f4(fa[0][i], fx[j], s3[i][j]);  // (fa[0]: the queries' validity by now)
                                 }
                         }
                     }
@@ -1641,7 +1704,8 @@ __global__ __launch_bounds__(WAVE, LONG ? 1 : CLM_WAVES) void k_cluster_dist_mfm
                     double d[16];
 #pragma unroll
                     for (int x = 0; x < 16; ++x) {
-                        const int nv = (int)s2[i][j][x], nmis = (3 * nv - (int)s1[i][j][x]) >> 2;
+                        const int nv2 = (int)s2[i][j][x], kx = EX ? (int)s3[i][j][x] : 0;
+                        const int nv = nv2 + kx, nmis = ((3 * nv2 - (int)s1[i][j][x]) >> 2) + kx;
 #ifdef CL_EXP_NO_EPILOGUE  // (timing experiment: the main loop alone)
                         d[x] = (double)(nv + nmis);
 #elif defined(CL_EXP_NO_LOG)  // (timing experiment, long form: the epilogue's stores without its logarithms -- positive finite values, wrong placements)
@@ -1756,6 +1820,44 @@ __global__ __launch_bounds__(APPLES_TPB) void k_cluster_dist_sd(SelectArgs a) {
     }
 }
 
+// The representatives' survivors of a context whose panels hold bytes beyond ACGT- as gaps, in front of every phase that reads
+// them.  The matrix-core pass over rep_packed counted (valid, mism) without the representative's such sites; a pair's true counts are
+// (valid + k, mism + k), k = the sites of the representative's mask plane (rep_x) under a letter of the query -- which can only make
+// the pair fail, and the pass's table was loosened where the overlap rule could have kept the smaller count out (set_params), so the
+// survivors are a superset.  A workgroup per query keeps the query's gap plane in LDS; a thread per 64-representative segment
+// recounts the survivors on flagged representatives (every survivor where the table was loosened: ex_all), tests them on the
+// integers against the rule's own table, rewrites the packed words and closes the segment up in place (the positions stay ascending).
+__global__ __launch_bounds__(APPLES_TPB) void k_cluster_rep_fix(SelectArgs a, int32_t *__restrict__ seg_slot, int32_t *__restrict__ seg_cnt) {
+    __shared__ uint4 sh_m[64];  // (G <= 64: the short forms)
+    const int64_t q = blockIdx.x;
+    const int G = a.G;
+    for (int g = threadIdx.x; g < G; g += APPLES_TPB) sh_m[g] = a.qpacked[(((q >> 4) * G + g) * 16 + (q & 15)) * 3];
+    __syncthreads();
+    const int64_t n_seg = a.rep_stride >> 6;
+    for (int64_t s = threadIdx.x; s < n_seg; s += APPLES_TPB) {
+        const int c = seg_cnt[q * n_seg + s];
+        int32_t *w = seg_slot + q * a.rep_stride + s * 64;
+        int out = 0;
+        for (int i = 0; i < c; ++i) {
+            const uint32_t pk = (uint32_t)w[i];
+            const int64_t j = s * 64 + (pk >> 26);
+            int valid = (int)((pk >> 13) & 0x1fffu), mism = (int)(pk & 0x1fffu);
+            const bool flagged = a.rep_x && j < a.n_reps && a.rep_bad[j];
+            if (flagged) {
+                int k = 0;
+                for (int g = 0; g < G; ++g) {
+                    const uint4 x = a.rep_x[(int64_t)g * a.rep_stride + j], m = sh_m[g];
+                    k += __popc(x.x & m.x) + __popc(x.y & m.y) + __popc(x.z & m.z) + __popc(x.w & m.w);
+                }
+                valid += k; mism += k;
+            }
+            if ((flagged || a.ex_all) && mism > a.ex_mmax[valid]) continue;
+            w[out++] = (int32_t)((pk & 0xfc000000u) | ((uint32_t)valid << 13) | (uint32_t)mism);
+        }
+        if (out != c) seg_cnt[q * n_seg + s] = out;
+    }
+}
+
 // (LONG: SelectArgs::cl_long -- the same launches with the kernels' long forms)
 template <bool LONG, int PHASE, int CAP = SELECT_CLUSTERS_ACC_CAP, bool LISTED = (PHASE == 4), int TPB = APPLES_TPB, bool SHORT_ONLY = false>
 static constexpr auto ksc() { return &k_select_clusters<PHASE, CAP, LISTED, TPB, SHORT_ONLY, LONG>; }
@@ -1763,6 +1865,11 @@ static constexpr auto ksc() { return &k_select_clusters<PHASE, CAP, LISTED, TPB,
 template <bool LONG>
 static int launch_select_clusters_t(apples_ctx *ctx, const SelectArgs &a, int64_t nq) {
     if (nq == 0) return 0;
+    if constexpr (!LONG)  // panels with bytes beyond ACGT- held as gaps: the survivors' true counts, the rule once more
+        if (a.ex_mmax && a.cl_xoff) {  // (a.seg_slot / a.seg_cnt are the workspace's: the kernel rewrites them through its own pointers)
+            hipLaunchKernelGGL(k_cluster_rep_fix, dim3((unsigned)nq), dim3(APPLES_TPB), 0, ctx->stream, a, ctx->ws.seg_slot, ctx->ws.seg_cnt);
+            HIP_TRY(ctx, hipGetLastError());
+        }
     // the slot bitmap and its 16-bit in-run prefixes (runs of 16 words: 262 144 slots); with clade blocks over emission indices
     size_t dyn = (size_t)(((a.e_of_slot ? std::max(a.n_e, a.n_members) : a.n_members) + 63) >> 6) * 10;
     if (a.e_of_slot) dyn = std::max<size_t>(dyn, 1024 * 16 + (SELECT_CLUSTERS_ACC_CAP + 1) * 4);  // (the short form's list lives in the bitmap's memory)
@@ -1806,7 +1913,15 @@ static int launch_select_clusters_t(apples_ctx *ctx, const SelectArgs &a, int64_
     }
     const int per_cu = (int)knob(ctx, "APPLES_CLUSTER_WGS", 8);  // tuning knob
     if (sd) hipLaunchKernelGGL(k_cluster_dist_sd<4>, dim3((unsigned)(ctx->n_cu * std::max(per_cu, 1))), dim3(APPLES_TPB), 0, ctx->stream, a);
-    else if (a.cl_mfma) hipLaunchKernelGGL(k_cluster_dist_mfma<LONG>, dim3((unsigned)(ctx->n_cu * 4 * (LONG ? 1 : CLM_WAVES))), dim3(WAVE), 0, ctx->stream, a);  // (18 KB of LDS per wavefront: eight per CU)
+    else if (a.cl_mfma) {
+        hipLaunchKernelGGL(k_cluster_dist_mfma<LONG>, dim3((unsigned)(ctx->n_cu * 4 * (LONG ? 1 : CLM_WAVES))), dim3(WAVE), 0, ctx->stream, a);  // (18 KB of LDS per wavefront: eight per CU)
+        if constexpr (!LONG)  // the tiles of the clusters with bytes beyond ACGT- (the launch above passed over them)
+            if (a.cl_xoff) {
+                HIP_TRY(ctx, hipGetLastError());
+                hipLaunchKernelGGL((k_cluster_dist_mfma<false, true>), dim3((unsigned)(ctx->n_cu * 4 * CLM_EX_WAVES)), dim3(WAVE), 0, ctx->stream, a);
+                HIP_TRY(ctx, hipGetLastError());
+            }
+    }
     else hipLaunchKernelGGL(k_cluster_dist<LONG>, dim3((unsigned)(ctx->n_cu * std::max(per_cu, 1))), dim3(APPLES_TPB), 0, ctx->stream, a);
     // the second form's last phase beside the first's, on the spare stream: a hundred-odd workgroups of 1 024 threads (their
     // rounds of member lookups are what such a workgroup takes: a quarter of the rounds of 256 threads) leave the chip idle
