@@ -658,7 +658,11 @@ int setup_alignment(apples_ctx *ctx, const apples_tree *t, const apples_alignmen
         // ... and in a clustered context that takes the fused route by representatives in its short forms (the conditions of the
         // panels below): the panels keep them as gaps, mask planes beside them say where they are (DevAlign::rep_x / x_rm)
         const bool cl_ex = !a.all_singleton && a.n_refs <= SELECT_CLUSTERS_MAX_SLOTS && !(ctx->dbg & APPLES_DBG_NO_FUSE);
-        a.ex_ok = (a.all_singleton || cl_ex) && dist_mfma_enabled(ctx) && a.L < 8192;
+        // ... and in a singleton context of GEMM_LONG_MIN_L sites and more on the K-split route, where the REFERENCE holds such a byte
+        // (decided below, once the rows are packed: a clean reference keeps today's rule and widens with the first such query):
+        // one mask plane per flagged slot (DevAlign::x_off / x_rows) and k_long_exotic_fix behind the pass
+        const bool ex_long = a.all_singleton && a.L >= GEMM_LONG_MIN_L && dist_mfma_enabled(ctx) && !(ctx->dbg & APPLES_DBG_NO_DIST_GEMM);
+        a.ex_ok = ((a.all_singleton || cl_ex) && dist_mfma_enabled(ctx) && a.L < 8192) || ex_long;
         std::vector<int32_t> cl_bad;  // clustered: the flagged slots
         int32_t *d_row_bad = nullptr;
         if (a.ex_ok) {
@@ -669,7 +673,29 @@ int setup_alignment(apples_ctx *ctx, const apples_tree *t, const apples_alignmen
         int exotic = 0;
         HIP_TRY(ctx, hipMemcpyAsync(&exotic, d_exotic, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        if (exotic && a.ex_ok) {
+        if (exotic && ex_long) {
+            // which slots (slot-major mask planes, no site lists: rows of these lengths hold hundreds of such bytes), and the 8-plane form
+            std::vector<int32_t> xoff((size_t)a.slots_pad, -1);
+            HIP_TRY(ctx, hipMemcpy(xoff.data(), d_row_bad, (size_t)a.n_rows * sizeof(int32_t), hipMemcpyDeviceToHost));
+            int32_t n_x = 0;
+            for (int64_t s = 0; s < a.n_rows; ++s) xoff[s] = xoff[s] ? n_x++ : -1;
+            int32_t *d_cnt = nullptr;
+            if (dev_upload(ctx, &a.x_off, xoff.data(), a.slots_pad)) return 1;
+            if (dev_alloc(ctx, &a.x_rows, (int64_t)n_x * a.G)) return 1;
+            if (dev_alloc(ctx, &d_cnt, n_x)) return 1;
+            std::vector<int32_t> cnt((size_t)n_x, 0);
+            int bad = hipMemcpyAsync(d_cnt, cnt.data(), (size_t)n_x * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
+                      launch_pack_exotic_mask_rows(ctx, a.x_off, a.x_rows, d_cnt) ||
+                      hipMemcpyAsync(cnt.data(), d_cnt, (size_t)n_x * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+                      hipStreamSynchronize(ctx->stream) != hipSuccess;  // (the vectors are locals)
+            dev_free(d_cnt);
+            if (bad) { if (ctx->err.empty()) ctx->err = "mask planes of the rows with bytes beyond ACGT-: failed"; return 1; }
+            a.ex_max = *std::max_element(cnt.begin(), cnt.end());
+            if (ensure_packed8(ctx)) return 1;
+            exotic = 0;
+        } else if (ex_long) {
+            a.ex_ok = false;  // a clean reference of these lengths: nothing kept beside the 2-plane rows
+        } else if (exotic && a.ex_ok) {
             // which slots, which sites (from the caller's rows: only the flagged rows are read again), and the 8-plane form
             std::vector<int32_t> bad((size_t)a.n_rows), off((size_t)a.n_rows + 1, 0);
             HIP_TRY(ctx, hipMemcpy(bad.data(), d_row_bad, (size_t)a.n_rows * sizeof(int32_t), hipMemcpyDeviceToHost));
@@ -2334,6 +2360,25 @@ static std::vector<int32_t> jc_bound_long_table(int L, double overlap, double f)
     return bound;
 }
 
+// A screen for counts that miss up to ex_max sites of the reference row (bytes beyond ACGT- held as gaps: a pair's true counts are
+// (valid + k, mism + k), 0 <= k <= ex_max): it must keep (valid, mism) whenever SOME k passes,
+//   loose[v] = v + max over j in [v, min(v + ex_max, L)] with bound[j] >= 0 of (bound[j] - j), -1 where there is no such j
+// -- a sliding-window maximum, O(L): the window's candidates in a queue of falling values.  Entries beyond L stay as they are.
+static std::vector<int32_t> loosen_bound(const std::vector<int32_t> &bound, int64_t L, int64_t ex_max) {
+    std::vector<int32_t> loose(bound), queue((size_t)L + 1);
+    int64_t head = 0, tail = 0, next = 0;  // queue[head .. tail): sites j of the window, bound[j] - j falling; next: first j not yet seen
+    for (int64_t v = 0; v <= L; ++v) {
+        for (const int64_t end = std::min(v + ex_max, L); next <= end; ++next) {
+            if (bound[next] < 0) continue;
+            while (tail > head && bound[queue[tail - 1]] - queue[tail - 1] <= bound[next] - next) --tail;
+            queue[tail++] = (int32_t)next;
+        }
+        while (head < tail && queue[head] < v) ++head;
+        loose[v] = head < tail ? std::max<int32_t>(-1, (int32_t)(v + bound[queue[head]] - queue[head])) : -1;
+    }
+    return loose;
+}
+
 int apples_set_params(apples_ctx *ctx, const apples_params *params) {
     HIP_TRY(ctx, hipSetDevice(ctx->device));  // the caller's thread may have another device current
     int model = ctx->params.model;
@@ -2375,12 +2420,8 @@ int apples_set_params(apples_ctx *ctx, const apples_params *params) {
                 // mism + k), 0 <= k <= ex_max, so the pass must keep (valid, mism) whenever SOME k passes: mmaxF[v] = max_k (mmax[v + k] - k).
                 // It differs from the rule only at the low end, where -V could keep the smaller count out; k_exotic_fix then tests
                 // every survivor against the rule itself.
-                std::vector<int32_t> mf(mmax);
-                bool loosened = false;
-                for (int64_t v = 0; v <= L; ++v)
-                    for (int64_t k = 1; k <= ctx->aln.ex_max && v + k <= L; ++k)
-                        if (mmax[v + k] >= 0 && mmax[v + k] - (int32_t)k > mf[v]) { mf[v] = mmax[v + k] - (int32_t)k; loosened = true; }
-                if (loosened) {
+                const std::vector<int32_t> mf = loosen_bound(mmax, L, ctx->aln.ex_max);
+                if (mf != mmax) {
                     if (dev_upload(ctx, &ctx->jc_mmax_true, mmax.data(), L + 1)) return 1;
                     mmax = mf;
                 }
@@ -2405,8 +2446,11 @@ int apples_set_params(apples_ctx *ctx, const apples_params *params) {
     // and from every table whose entry for no valid site does not pass; a clustered context whose table lets it pass gets no screen
     // and so stays on the general route)
     if (ctx->has_aln && ctx->params.model == APPLES_JC69 && (ctx->aln.ref_f4 || ctx->aln.rep_f4) && ctx->aln.L >= GEMM_LONG_MIN_L) {
-        const std::vector<int32_t> bound = !bound_long.empty() ? bound_long
-                                           : jc_bound_long_table(ctx->aln.L, params->overlap_frac, params->filt_threshold);
+        std::vector<int32_t> bound = !bound_long.empty() ? bound_long
+                                     : jc_bound_long_table(ctx->aln.L, params->overlap_frac, params->filt_threshold);
+        // (reference rows with bytes beyond ACGT-, DevAlign::x_off: the pass counts them as gaps and k_long_exotic_fix tests every
+        // survivor against the rule itself -- the table through jc_lut where the caller supplies one)
+        if (ctx->aln.x_off && ctx->aln.ex_max > 0) bound = loosen_bound(bound, ctx->aln.L, ctx->aln.ex_max);
         if (ctx->aln.ref_f4 || bound[0] < 0) {
             if (dev_upload(ctx, &ctx->jc_bound_long, bound.data(), (int64_t)bound.size())) return 1;
             HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -2458,7 +2502,7 @@ void apples_ctx_destroy(apples_ctx *ctx) {
     DevAlign &a = ctx->aln;
     dev_free(a.raw); dev_free(a.d_slot_row); dev_free(a.packed); dev_free(a.ref_f4); dev_free(a.rep_f4); dev_free(a.rep_boff); dev_free(a.rep_loff); dev_free(a.loose_mp); dev_free(a.blk_rec_i); dev_free(a.blk_rec_e); dev_free(a.blk_rec_c); dev_free(a.blk_rec_p); dev_free(a.blk_pk_i); dev_free(a.blk_pk_e); dev_free(a.blk_stat[0]); dev_free(a.blk_stat[1]); dev_free(a.rep_soff); dev_free(a.cl_order); dev_free(a.mem_block); dev_free(a.blk_root); dev_free(a.blk_rslot); dev_free(a.blk_nodes); dev_free(a.e_of_slot); dev_free(a.e_of_blk); dev_free(a.e_node); dev_free(a.lvl_e); dev_free(a.rep_packed); dev_free(a.packed_rm); dev_free(a.aa_rep_idx); dev_free(a.aa_rep_mask); dev_free(a.aa_cm_idx); dev_free(a.aa_cm_mask); dev_free(a.aa_idx); dev_free(a.aa_mask); dev_free(a.sd_ref4); dev_free(a.sd_nvr); dev_free(a.aa_rows); dev_free(a.aa_mrows); dev_free(ctx->sd_tq4); dev_free(ctx->sd_list_img); dev_free(ctx->sd_list_ints); dev_free(a.slot_node); dev_free(a.slot_level); dev_free(a.lvl_slots);
     dev_free(a.slot_rep); dev_free(a.slot_mpos); dev_free(a.rep_slot); dev_free(a.rep_moff); dev_free(a.mem_slot);
-    dev_free(a.rep_x); dev_free(a.rep_bad); dev_free(a.x_rm); dev_free(a.cl_xoff);
+    dev_free(a.rep_x); dev_free(a.rep_bad); dev_free(a.x_rm); dev_free(a.cl_xoff); dev_free(a.x_off); dev_free(a.x_rows);
     dev_free(ctx->jc_lut); dev_free(ctx->jc_mmax); dev_free(ctx->jc_mmax_true); dev_free(ctx->jc_bound_long); dev_free(ctx->blosum); dev_free(ctx->d_col_perm); dev_free(ctx->d_col_node);
     dev_free(ctx->d_col_level);
     for (int i = 0; i < 8; ++i)
@@ -3040,7 +3084,7 @@ const char *apples_describe(apples_ctx *ctx) {
              "{\"device\": \"%s\", \"compute_units\": %d, \"n_nodes\": %d, \"height\": %d, \"max_children\": %d, \"n_rows\": %lld, "
              "\"n_refs\": %lld, \"n_reps\": %lld, \"length\": %d, \"code_planes\": %d, \"all_singleton\": %d, "
              "\"packed_bytes\": %lld, \"batch\": %lld, \"sweep_workgroups\": %d, \"sweep_team_cap\": %lld, \"sweep_big_workgroups\": %d, \"jc_lut\": %d, \"sweep\": \"%s\", "
-             "\"fused_distance_pass\": \"%s\", \"gemm_split_sites\": %d, \"k_split_launches\": %lld, \"cluster_k_split_launches\": %lld, \"fp4_reference_image_bytes\": %lld, \"sweep_layout\": \"%s\", \"cluster_fused\": %d, "
+             "\"fused_distance_pass\": \"%s\", \"gemm_split_sites\": %d, \"k_split_launches\": %lld, \"k_split_exotic_fixes\": %lld, \"cluster_k_split_launches\": %lld, \"fp4_reference_image_bytes\": %lld, \"sweep_layout\": \"%s\", \"cluster_fused\": %d, "
              "\"scoredist_filter\": %d, \"scoredist_image_bytes\": %lld, \"cluster_blocks\": %d, \"block_items_last_batch\": %d, \"block_tiles_last_batch\": %d, "
              "\"exotic_symbols_as_gaps\": %d, \"exotic_sites_max_per_row\": %d, \"eight_plane_copy\": %d, \"cluster_exotic_clusters\": %d, "
              "\"ragged_rows\": %d, \"row_small\": %lld, \"big_rows\": %lld, \"big_rows_last_batch\": %d, \"full_rows_for_good\": %d, "
@@ -3057,6 +3101,7 @@ const char *apples_describe(apples_ctx *ctx) {
              : (a.rep_f4 && ctx->jc_bound_long && !(ctx->dbg & (APPLES_DBG_NO_DIST_GEMM | APPLES_DBG_NO_FUSE))) ? "fp4 gemm, k-split over representatives"
              : (a.planes == 2 && dist_mfma_enabled(ctx) && a.L < GEMM_LONG_MIN_L ? "fp4 mfma, bit-plane fed" : "valu"),
              dist_gemm_long_usable(ctx) ? GEMM_SPLIT_STEPS * 64 : 0, (long long)ctx->gemm_long_launches,
+             (long long)ctx->long_exotic_fixes,  // ... and of k_long_exotic_fix behind it (reference rows with bytes beyond ACGT-: DevAlign::x_off)
              (long long)ctx->cluster_long_launches,  // ... of the same kernel over the representatives' image (clustered contexts of 8 192+ sites)
              (long long)(a.ref_f4 ? a.slots_pad * (int64_t)a.G * 128 : 0),
              // how the level-loop sweep knows a query's subtree: merged level lists / node bits in LDS / tagged node map

@@ -136,11 +136,18 @@ struct DevAlign {
     //   * ex_off / ex_site: per slot the sites that hold such a byte -- k_exotic_fix adds them back to the counts of the fused
     //     pass's survivors (a site where the row has such a byte and the query a letter is valid and a mismatch).
     bool ex_ok = false;           // the context takes this route (JC69, matrix-core passes enabled, L < 8192; singleton clusters, or a
-                                  // clustered context on the fused route by representatives: rep_x / x_rm below in place of ex_off / ex_site)
+                                  // clustered context on the fused route by representatives: rep_x / x_rm below in place of ex_off / ex_site;
+                                  // from 8 192 sites on: singleton contexts on the K-split route whose reference holds such a byte, x_off / x_rows)
     uint4 *packed8 = nullptr;     // [G][9][slots_pad]; built with the first such byte, in the reference or in a query block
     int32_t *ex_off = nullptr;    // [n_rows + 1] CSR over slots, or nullptr: the reference rows hold no such byte
     uint16_t *ex_site = nullptr;  // [ex_off[n_rows]] sites, ascending per slot
     int32_t ex_max = 0;           // most such sites in one row
+    // ... the same in a singleton context of GEMM_LONG_MIN_L sites and more (k_jc69_gemm_long's EX form, then dist.hip: k_long_exotic_fix):
+    // no site lists -- rows hold hundreds of such bytes -- but one mask plane per flagged slot, slot-major: the plane of slot s is the G
+    // words x_rows[x_off[s] * G ..], the bit order of the 2-plane rows' gap plane, bit = the site holds such a byte
+    // (pack.hip: k_pack_exotic_mask_rows), so that k = sum over the words of popc(mask & the query's gap plane)
+    int32_t *x_off = nullptr;     // [slots_pad] index of the slot's plane in x_rows, -1: the row holds no such byte (or the slot no row)
+    uint4 *x_rows = nullptr;      // [flagged slots][G]
     // clustered references (fused selection by representatives, select.hip k_select_clusters):
     uint4 *packed_rm = nullptr;   // the member rows cluster by cluster, interleaved per plane word (dist.hip:k_cluster_major): [n_refs * G*3]
     uint4 *rep_packed = nullptr;  // [G][3][reps_pad] the representatives' rows, in representative order
@@ -356,6 +363,7 @@ struct apples_ctx {
                                        // (api.hip: jc_bound_long_table).  With one: the largest mismatch count whose TABULATED distance
                                        // passes.  The kernel's own exact test decides.  NOT jc_mmax: that one switches k_jc69 onto the table
     int64_t gemm_long_launches = 0;    // launches of k_jc69_gemm_long so far (describe(): "k_split_launches")
+    int64_t long_exotic_fixes = 0;     // launches of k_long_exotic_fix behind it (describe(): "k_split_exotic_fixes")
     int64_t cluster_long_launches = 0; // ... over the representatives' image of a clustered context (describe(): "cluster_k_split_launches")
     double *blosum = nullptr;  // 21x21 table (row/col 20 = gap -> 0)
     uint8_t *sd_tq4 = nullptr; // [20][20] fp4 codes of the table rounded down to the grid {0, .5, 1, 1.5, 2, 3, 4, 6} / 4 (dist_sd.hip)
@@ -427,6 +435,8 @@ int launch_pack_aa(apples_ctx *ctx, const uint8_t *d_raw, int64_t n_rows, int L,
                    int64_t slots_pad, bool query_layout, hipStream_t st = nullptr, const int32_t *d_src_row = nullptr);
 // the mask panels of a clustered context with bytes beyond ACGT- (DevAlign::rep_x / x_rm), from a.raw; d_rep_x may be nullptr
 int launch_pack_exotic_masks(apples_ctx *ctx, const int32_t *d_cl_xoff, uint4 *d_x_rm, uint4 *d_rep_x);
+// ... one plane per flagged slot (DevAlign::x_off / x_rows); d_x_cnt[x_off[slot]] += the slot's such sites (the caller zeroes it)
+int launch_pack_exotic_mask_rows(apples_ctx *ctx, const int32_t *d_x_off, uint4 *d_x_rows, int32_t *d_x_cnt);
 // dist.hip
 int launch_counts(apples_ctx *ctx, const QueryBlock &qb, int64_t q0, int64_t nq, int tile, double *d_dist,
                   uint32_t *d_counts);
@@ -609,6 +619,11 @@ int launch_counts_listed(apples_ctx *ctx, const QueryBlock &qb, int64_t q0, int6
                          const int32_t *qcount, double *d_dist, double *segmin_d, int32_t *segmin_i);
 // the fused matrix-core pass's survivors (packed words in seg_slot) on reference rows with bytes beyond ACGT-: exact counts, the
 // threshold once more, n_surv[query] = how many stay (k_select_fast: SelectArgs::seg_surv)
+// ... and behind k_jc69_gemm_long's EX form (slots and boxed integer totals in k_jc69 MODE 1's buffers): the counts of every
+// entry completed from the mask planes, the exact test, k_jc69 MODE 1's format left behind.  row_off / masks: per row of the pass's
+// operand image (rows of them) the index of its mask plane or -1, and the planes (DevAlign::x_off / x_rows)
+int launch_long_exotic_fix(apples_ctx *ctx, const QueryBlock &qb, int64_t q0, int64_t nq, double *seg_d, int32_t *seg_slot,
+                           int32_t *seg_cnt, const int32_t *row_off, const uint4 *masks, int64_t rows);
 int launch_exotic_fix(apples_ctx *ctx, const QueryBlock &qb, int64_t q0, int64_t nq, int32_t *seg_slot, const int32_t *seg_cnt,
                       int32_t *n_surv);  // (diagnostic form: api.hip does the same inside k_select_fast)
 bool exact8_rows(const apples_ctx *ctx, const QueryBlock &qb);  // the bit-plane kernels take the 8-plane forms for this block

@@ -628,8 +628,12 @@ int launch_counts_fused(apples_ctx *ctx, const QueryBlock &qb, int64_t q0, int64
         return dist_gemm_usable(ctx) ? launch_counts_gemm(ctx, qb, q0, nq, seg_slot, seg_cnt)
                                      : launch_mfma<1>(ctx, qb, q0, nq, seg_d, nullptr, seg_slot, seg_cnt);
     // alignments of GEMM_LONG_MIN_L sites and more, ACGT- blocks: the K-split GEMM writes the format of k_jc69 MODE 1
-    if (dist_gemm_long_usable(ctx) && qb.qf4 && qb.planes == 2 && !exact8_rows(ctx, qb))
-        return launch_counts_gemm_long(ctx, qb, q0, nq, seg_d, seg_slot, seg_cnt);
+    // (a context whose reference rows hold bytes beyond ACGT- -- DevAlign::x_off; its blocks carry 8-plane copies for the full rows,
+    // which is not what keeps a block off this route: QueryBlock::exact8 is -- runs the kernel's EX form and completes the counts behind it)
+    if (dist_gemm_long_usable(ctx) && qb.qf4 && qb.planes == 2 && (ctx->aln.x_off ? !qb.exact8 : !exact8_rows(ctx, qb))) {
+        if (launch_counts_gemm_long(ctx, qb, q0, nq, seg_d, seg_slot, seg_cnt)) return 1;
+        return ctx->aln.x_off ? launch_long_exotic_fix(ctx, qb, q0, nq, seg_d, seg_slot, seg_cnt, ctx->aln.x_off, ctx->aln.x_rows, ctx->aln.slots_pad) : 0;
+    }
     if (!exact8_rows(ctx, qb)) launch_jc69_tile<2, 1>(ctx, qb, q0, nq, tile, seg_d, nullptr, seg_slot, seg_cnt, nullptr, nullptr);
     else launch_jc69_tile<8, 1>(ctx, qb, q0, nq, tile, seg_d, nullptr, seg_slot, seg_cnt, nullptr, nullptr);
     HIP_TRY(ctx, hipGetLastError());
@@ -972,6 +976,87 @@ int launch_exotic_fix(apples_ctx *ctx, const QueryBlock &qb, int64_t q0, int64_t
                        qb.raw + q0 * (int64_t)a.L, a.L, a.ex_off, a.ex_site, ctx->jc_mmax_true ? ctx->jc_mmax_true : ctx->jc_mmax,
                        ctx->jc_mmax_true ? 1 : 0, n_surv);
     HIP_TRY(ctx, hipGetLastError());
+    return 0;
+}
+
+// ---- the same behind the K-split pass (dist_gemm.hip: k_jc69_gemm_long's EX form; alignments of GEMM_LONG_MIN_L sites and more) ----
+// That pass leaves, per 64-row segment of every query, the pairs its loosened screen let through: row index in seg_slot, the
+// packed total (valid << 16) | mism -- such bytes counted as gaps -- in the low word of the fp64 entry, their number in seg_cnt.
+// Rows of these lengths hold hundreds of such bytes, so k is not a walk over site lists but a bit count: every flagged row has a
+// mask plane of G uint4 words in the bit order of the gap planes (pack.hip: k_pack_exotic_mask_rows), and
+// k = sum over the words of popc(mask & the query's gap plane).
+//
+// One workgroup per query.  It stages the query's gap plane in LDS once (G words of 16 bytes, 8 KB at most; the tiled query
+// layout has them 48 bytes apart).  Its wavefronts then deal the query's segments among themselves 64 at a time: one read brings 64
+// counts, a ballot names the live ones.  In a live segment lane e holds entry e; for every entry on a flagged row (a ballot
+// loop, the plane's index through a readlane) all 64 lanes read the row's plane -- consecutive kilobytes --, AND it with the
+// staged plane, count, and add up across the wavefront: the entry's k.  Then every lane evaluates its own entry with
+// jc69_from_counts on (mism + k, valid + k) -- the bit-plane kernel's test, literally, so its bytes -- and the survivors are
+// compacted by ballot, in row order, to the start of the segment: k_jc69 MODE 1's format.  A lane reads its entry before any lane
+// of the wavefront writes, and no other wavefront touches the segment.
+// Padding rows and all-gap queries have k = 0 and valid = 0: the exact test drops them.
+// row_off: row of the pass -> index of its plane in `masks`, -1 for a clean row (today DevAlign::x_off over the slots; the
+// representatives' image of a clustered context would bring a map of its own).
+namespace {
+__global__ __launch_bounds__(APPLES_TPB) void k_long_exotic_fix(int32_t *__restrict__ seg_slot, int32_t *__restrict__ seg_cnt,
+                                                               double *__restrict__ seg_d, int64_t stride, const uint4 *__restrict__ qp,
+                                                               int64_t q0, int G, int L, const int32_t *__restrict__ row_off,
+                                                               const uint4 *__restrict__ masks, double overlap, double thr,
+                                                               const double *__restrict__ lut) {
+    __shared__ uint4 qm[512];  // the query's gap plane (G <= 512: 65 535 sites)
+    const int64_t q = blockIdx.x, qa = q0 + q;  // row of the launch's buffers; query of the block
+    const uint4 *qsrc = qp + ((qa >> 4) * G * 16 + (qa & 15)) * 3;
+    for (int g = threadIdx.x; g < G; g += APPLES_TPB) qm[g] = qsrc[(int64_t)g * 48];
+    __syncthreads();
+    const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
+    const int64_t n_seg = stride >> 6;
+    int32_t *cnt_q = seg_cnt + q * n_seg;
+    for (int64_t s0 = (int64_t)wv * WAVE; s0 < n_seg; s0 += APPLES_TPB) {  // 64 segments per wavefront and trip
+        const int c_mine = s0 + lane < n_seg ? cnt_q[s0 + lane] : 0;
+        for (unsigned long long live = __ballot(c_mine > 0); live; live &= live - 1) {
+            const int sl = __builtin_ctzll(live);
+            const int c = __builtin_amdgcn_readlane(c_mine, sl);
+            const int64_t o = q * stride + (s0 + sl) * 64 + lane;
+            const bool on = lane < c;
+            const int32_t row = on ? seg_slot[o] : 0;
+            const uint32_t t = on ? (uint32_t)__double2loint(seg_d[o]) : 0u;
+            const int xo = on ? row_off[row] : -1;
+            uint32_t k = 0;
+            for (unsigned long long fl = __ballot(xo >= 0); fl; fl &= fl - 1) {
+                const int e = __builtin_ctzll(fl);
+                const uint4 *x = masks + (int64_t)__builtin_amdgcn_readlane(xo, e) * G;
+                uint32_t n = 0;
+                for (int g = lane; g < G; g += WAVE) {
+                    const uint4 xv = x[g], m = qm[g];
+                    n += __popc(xv.x & m.x) + __popc(xv.y & m.y) + __popc(xv.z & m.z) + __popc(xv.w & m.w);
+                }
+                for (int sft = WAVE / 2; sft > 0; sft >>= 1) n += __shfl_xor(n, sft, WAVE);
+                if (lane == e) k = n;
+            }
+            double d = -1.0;
+            if (on) d = jc69_from_counts((t & 0xffffu) + k, (t >> 16) + k, L, overlap, lut);
+            const bool keep = d >= 0 && d <= thr;
+            const unsigned long long m = __ballot(keep);
+            if (keep) {
+                const int64_t w = q * stride + (s0 + sl) * 64 + __popcll(m & ((1ull << lane) - 1ull));
+                seg_slot[w] = row;
+                seg_d[w] = d;
+            }
+            if (lane == 0) cnt_q[s0 + sl] = __popcll(m);
+        }
+    }
+}
+}  // namespace
+
+int launch_long_exotic_fix(apples_ctx *ctx, const QueryBlock &qb, int64_t q0, int64_t nq, double *seg_d, int32_t *seg_slot,
+                           int32_t *seg_cnt, const int32_t *row_off, const uint4 *masks, int64_t rows) {
+    if (nq == 0) return 0;
+    const DevAlign &a = ctx->aln;
+    if (a.G > 512 || qb.planes != 2) { ctx->err = "k_long_exotic_fix: needs 2-plane query rows of at most 65 535 sites"; return 1; }
+    hipLaunchKernelGGL(k_long_exotic_fix, dim3((unsigned)nq), dim3(APPLES_TPB), 0, ctx->stream, seg_slot, seg_cnt, seg_d, rows,
+                       qb.packed, q0, a.G, a.L, row_off, masks, ctx->params.overlap_frac, ctx->params.filt_threshold, ctx->jc_lut);
+    HIP_TRY(ctx, hipGetLastError());
+    ++ctx->long_exotic_fixes;
     return 0;
 }
 

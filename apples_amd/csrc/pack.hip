@@ -225,6 +225,46 @@ int launch_pack_exotic_masks(apples_ctx *ctx, const int32_t *d_cl_xoff, uint4 *d
     return 0;
 }
 
+// The same for a singleton context of GEMM_LONG_MIN_L sites and more (DevAlign::x_off / x_rows): one plane per flagged slot,
+// slot-major -- the G words of slot s at x_rows[x_off[s] * G], so that a wavefront reads a row's plane in whole kilobytes
+// (dist.hip: k_long_exotic_fix).  Item = slot, a thread = one 32-site word, clean slots are not read.  The row's number of
+// such sites is summed into x_cnt[x_off[s]] (one atomic per word group that holds any): the host takes ex_max from it.
+__global__ __launch_bounds__(APPLES_TPB) void k_pack_exotic_mask_rows(const uint8_t *__restrict__ raw, int L, int G, int64_t n_rows,
+                                                                      const int32_t *__restrict__ slot_row, const int32_t *__restrict__ x_off,
+                                                                      uint4 *__restrict__ x_rows, int32_t *__restrict__ x_cnt) {
+    const int64_t idx = (int64_t)blockIdx.x * APPLES_TPB + threadIdx.x;
+    const int W4 = G * 4;
+    const int64_t slot = idx / W4;
+    const int w = (int)(idx - slot * W4);
+    const int xo = slot < n_rows ? x_off[slot] : -1;
+    uint32_t x = 0;
+    if (xo >= 0 && w * 32 < L) {
+        const uint8_t *src = raw + (int64_t)slot_row[slot] * L + w * 32;
+        const int nb = min(32, L - w * 32);
+        for (int i = 0; i < nb; ++i) {
+            const uint32_t b = src[i];
+            x |= (uint32_t)!(b == '-' || b == 'A' || b == 'C' || b == 'G' || b == 'T') << i;
+        }
+    }
+    // (W4 is a multiple of 4: the four words of a group sit in four consecutive lanes of one wavefront)
+    const uint4 px = make_uint4(x, __shfl_down(x, 1, 64), __shfl_down(x, 2, 64), __shfl_down(x, 3, 64));
+    if (xo >= 0 && (w & 3) == 0) {
+        x_rows[(int64_t)xo * G + (w >> 2)] = px;
+        const int n = __popc(px.x) + __popc(px.y) + __popc(px.z) + __popc(px.w);
+        if (n) atomicAdd(x_cnt + xo, n);
+    }
+}
+
+int launch_pack_exotic_mask_rows(apples_ctx *ctx, const int32_t *d_x_off, uint4 *d_x_rows, int32_t *d_x_cnt) {
+    const DevAlign &a = ctx->aln;
+    const int64_t total = a.n_rows * (int64_t)a.G * 4;
+    if (total == 0) return 0;
+    hipLaunchKernelGGL(k_pack_exotic_mask_rows, dim3((unsigned)((total + APPLES_TPB - 1) / APPLES_TPB)), dim3(APPLES_TPB), 0, ctx->stream,
+                       a.raw, a.L, a.G, a.n_rows, a.d_slot_row, d_x_off, d_x_rows, d_x_cnt);
+    HIP_TRY(ctx, hipGetLastError());
+    return 0;
+}
+
 // scoredist layout: residue index per site, a2i of apples/distance.py:418-678 (ARNDCQEGHILKMFPSTWYV
 // both cases -> 0..19, every other byte -> 0) with '-' -> 20 (a zero row/column of the table, so
 // gapped sites add +0.0 exactly as nondash*BLOSUM45[...] does at distance.py:706).

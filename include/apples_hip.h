@@ -230,7 +230,7 @@ enum { APPLES_T_PACK = 0, APPLES_T_DIST = 1, APPLES_T_SELECT = 2, APPLES_T_SWEEP
 int apples_last_timing(const apples_ctx *ctx, double *ms, int32_t n);
 
 /* Introspection: device name, packed layout, workspace sizes (JSON text, owned by ctx).  Which route a context takes is in here:
- * "sweep_layout" (lean / merge / bits / map / scan), "fused_distance_pass" (fp4 gemm, linear threshold / fp4 gemm, threshold table / fp4 gemm, k-split / fp4 gemm, k-split over representatives / fp4 mfma / valu), "gemm_split_sites" (sites per split of the k-split route, else 0), "k_split_launches" (launches of that route's kernel so far), "cluster_k_split_launches" (the same kernel over the representatives' image: clustered contexts of 8 192 to 65 535 sites), "code_planes",
+ * "sweep_layout" (lean / merge / bits / map / scan), "fused_distance_pass" (fp4 gemm, linear threshold / fp4 gemm, threshold table / fp4 gemm, k-split / fp4 gemm, k-split over representatives / fp4 mfma / valu), "gemm_split_sites" (sites per split of the k-split route, else 0), "k_split_launches" (launches of that route's kernel so far), "k_split_exotic_fixes" (launches of the kernel that completes the counts behind it where reference rows of 8 192 to 65 535 sites hold bytes beyond ACGT-), "cluster_k_split_launches" (the same kernel over the representatives' image: clustered contexts of 8 192 to 65 535 sites), "code_planes",
  * "cluster_fused", "cluster_blocks", "max_children", "height", "exotic_symbols_as_gaps" / "eight_plane_copy" (bytes beyond ACGT-),
  * "batch" (queries per device batch), "ragged_rows" / "row_small" / "big_rows" / "big_rows_last_batch" / "full_rows_for_good" (the
  * clustered route's observation rows: DESIGN.md section 3). */
