@@ -1187,7 +1187,7 @@ void free_block(apples_ctx *ctx, QueryBlock *qb) {
     blk_free(ctx, qb->table); blk_free(ctx, qb->raw); blk_free(ctx, qb->packed); blk_free(ctx, qb->qf4);
     blk_free(ctx, qb->aa_idx); blk_free(ctx, qb->aa_mask); blk_free(ctx, qb->self_slot); blk_free(ctx, qb->out);
     blk_free(ctx, qb->sd_q4); blk_free(ctx, qb->sd_nvq);
-    blk_free(ctx, qb->packed8); blk_free(ctx, qb->q_ex); blk_free(ctx, qb->ex_idx);
+    blk_free(ctx, qb->packed8); blk_free(ctx, qb->q_ex); blk_free(ctx, qb->ex_idx); blk_free(ctx, qb->qx); blk_free(ctx, qb->qx_idx);
     if (qb->ex_block) { free_block(ctx, qb->ex_block); delete qb->ex_block; }
     *qb = QueryBlock();
 }
@@ -1286,10 +1286,54 @@ int take_exotic(apples_ctx *ctx, hipStream_t st, int *exotic) {
 
 int make_block(apples_ctx *ctx, const uint8_t *queries, int64_t n, const int32_t *self_row, QueryBlock *qb);
 
+// The cap of the matrix-core route below (APPLES_QUERY_EXOTIC_CAP overrides): a query takes it while min(its bytes beyond ACGT-, the
+// most such bytes in a reference row) -- what it adds to the screen's "+ D" -- stays within the cap.  The survivor volume of the
+// loosened launch grows steeply with D: measured at config 3's shape against the 8-plane pass of the same block (DESIGN.md section 3,
+// profiles/query_exotic_c3.txt), D = 1 is 4 % ahead, D = 4 behind, D = 64 six times slower.  A clean reference has D = 0 whatever
+// the queries hold: no query is kept off the route there (6.6 x ahead of the 8-plane pass).
+constexpr int64_t QUERY_EXOTIC_CAP = 1;
+
+// The screen of the launches over a block whose queries hold up to `top` bytes beyond ACGT- as gaps in their fp4 image
+// (apples_ctx::jc_mmax_q; the arithmetic: dist.hip, k_query_exotic_fix).  A pair's true counts are (v + t, m + t - j): t <= T =
+// ex_max + top sites the pass took for gaps, j <= D = min(ex_max, top) of them matching (the same such byte in both rows).  It
+// survives the rule if m + t - j <= rule[v + t], so the screen keeps every (v, m) with
+//   m <= max over t in [0, T], v + t <= L, rule[v + t] >= 0 of (rule[v + t] - t) + D
+// (-1 where no t qualifies).  The window matters at the table's lower end only, where the overlap rule -V keeps the smaller count
+// out; "+ D" is the whole loosening elsewhere, and D = 0 for a clean reference.  Built once and rebuilt when a block asks for
+// more: a looser screen is still a superset, k_query_exotic_fix tests every survivor against the rule itself.
+int query_screen(apples_ctx *ctx, int64_t top) {
+    const int64_t L = ctx->aln.L, D = std::min<int64_t>(ctx->aln.ex_max, top);
+    if (ctx->h_mmax.empty()) { ctx->err = "query_screen: no integer form of the threshold rule"; return 1; }
+    if (ctx->jc_mmax_q && ctx->mmax_q_top >= top && ctx->mmax_q_D >= D) return 0;
+    const std::vector<int32_t> &rule = ctx->h_mmax;
+    const int64_t T = std::min<int64_t>(L, (int64_t)ctx->aln.ex_max + top);
+    std::vector<int32_t> scr((size_t)L + 1, -1);
+    for (int64_t v = 0; v <= L; ++v) {
+        int64_t best = INT64_MIN;
+        for (int64_t t = 0, end = std::min(T, L - v); t <= end; ++t)
+            if (rule[v + t] >= 0) best = std::max(best, (int64_t)rule[v + t] - t);
+        if (best != INT64_MIN) scr[v] = (int32_t)std::max<int64_t>(-1, std::min(v, best + D));
+    }
+    dev_free(ctx->jc_mmax_q);
+    ctx->jc_mmax_q = nullptr;
+    if (dev_upload(ctx, &ctx->jc_mmax_q, scr.data(), L + 1)) return 1;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (scr is a local)
+    ctx->mmax_q_top = top; ctx->mmax_q_D = D;
+    return 0;
+}
+
 // A packed 2-plane block of an ex_ok context whose queries carry bytes beyond ACGT- (the context's flag said so): the reference's
-// 8-plane form comes into being, the block gets its own, and the queries concerned are placed by the 8-plane kernels -- a few of
-// them: as a block of their own (ex_block: placed behind the main pass, whose placements for them are overwritten); many (more
-// than a twentieth of the block): the whole block (exact8: no matrix-core pass for it).  `queries` / `self_row`: the caller's.
+// 8-plane form comes into being, the block gets its own (everything that writes full rows reads them), and the queries concerned
+// are placed in one of three ways --
+//   * a few of them (a twentieth of the block at most): as a block of their own by the 8-plane kernels (ex_block: placed behind the
+//     main pass, whose placements for them are overwritten);
+//   * more, in a singleton context of fewer than 8 192 sites whose fused pass writes the packed survivor word: the block stays on
+//     the matrix-core pass -- its fp4 image holds such bytes as gaps --, gets one mask plane per flagged query (QueryBlock::qx), its
+//     launches a loosened screen (query_screen) and k_query_exotic_fix behind them.  A query that would loosen the screen by more
+//     than QUERY_EXOTIC_CAP does not take the route: those go to the ex_block by the few-rule above;
+//   * else (too many of those as well, a clustered context, the K-split route): the whole block through the 8-plane kernels
+//     (exact8: no matrix-core pass for it).
+// `queries` / `self_row`: the caller's.
 int exotic_queries(apples_ctx *ctx, QueryBlock *qb, const uint8_t *queries, const int32_t *self_row) {
     DevAlign &a = ctx->aln;
     if (ensure_packed8(ctx)) return 1;
@@ -1305,7 +1349,42 @@ int exotic_queries(apples_ctx *ctx, QueryBlock *qb, const uint8_t *queries, cons
     for (int64_t i = 0; i < qb->n; ++i)
         if (flag[i]) idx.push_back((int32_t)i);
     if (idx.empty()) return 0;
-    if ((int64_t)idx.size() > std::min<int64_t>(std::max<int64_t>(16, qb->n / 20), 2048)) { qb->exact8 = true; return 0; }
+    const int64_t few = std::min<int64_t>(std::max<int64_t>(16, qb->n / 20), 2048);
+    if ((int64_t)idx.size() > few) {
+        const bool in_scope = a.all_singleton && ctx->params.model == APPLES_JC69 && a.planes == 2 && a.L < 8192 && qb->qf4 &&
+                              ctx->jc_mmax && !ctx->h_mmax.empty() && !knob_on(ctx, "APPLES_NO_MMAX");
+        if (!in_scope) { qb->exact8 = true; return 0; }
+        // the flagged queries' mask planes and how many such bytes each holds
+        std::vector<int32_t> map((size_t)qb->n_pad, -1), cnt(idx.size(), 0);
+        for (size_t k = 0; k < idx.size(); ++k) map[idx[k]] = (int32_t)k;
+        blk_free(ctx, qb->qx); blk_free(ctx, qb->qx_idx);
+        qb->qx = nullptr; qb->qx_idx = nullptr;
+        int32_t *d_cnt = nullptr;
+        if (blk_alloc(ctx, &qb->qx_idx, qb->n_pad) || blk_alloc(ctx, &qb->qx, (int64_t)idx.size() * a.G) || dev_alloc(ctx, &d_cnt, (int64_t)idx.size())) return 1;
+        int bad = hipMemcpyAsync(qb->qx_idx, map.data(), map.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
+                  hipMemcpyAsync(d_cnt, cnt.data(), cnt.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
+                  launch_pack_query_masks(ctx, qb->raw, qb->n, qb->qx_idx, qb->qx, d_cnt) ||
+                  hipMemcpyAsync(cnt.data(), d_cnt, cnt.size() * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+                  hipStreamSynchronize(ctx->stream) != hipSuccess;  // (the vectors are locals)
+        dev_free(d_cnt);
+        if (bad) { if (ctx->err.empty()) ctx->err = "mask planes of the queries with bytes beyond ACGT-: failed"; return 1; }
+        const int64_t cap = knob(ctx, "APPLES_QUERY_EXOTIC_CAP", QUERY_EXOTIC_CAP);
+        std::vector<int32_t> over;
+        int32_t top = 0;
+        for (size_t k = 0; k < idx.size(); ++k) {
+            if (std::min<int64_t>(cnt[k], a.ex_max) > cap) over.push_back(idx[k]);
+            else top = std::max(top, cnt[k]);
+        }
+        if ((int64_t)over.size() > few || over.size() == idx.size()) {  // (nobody left for the route: as before)
+            blk_free(ctx, qb->qx); blk_free(ctx, qb->qx_idx);
+            qb->qx = nullptr; qb->qx_idx = nullptr;
+            qb->exact8 = true;
+            return 0;
+        }
+        qb->qx_top = top;
+        idx.swap(over);  // (their placements by the main pass are overwritten)
+        if (idx.empty()) return 0;
+    }
     std::vector<uint8_t> rows(idx.size() * (size_t)a.L);
     std::vector<int32_t> self(idx.size(), -1);
     for (size_t k = 0; k < idx.size(); ++k) {
@@ -1664,10 +1743,14 @@ int run_block_main(apples_ctx *ctx, QueryBlock &qb, const Feeder *feed) {
     // against 69.2 -- lists of 3 126 observed leaves per query outgrow the Infinity Cache in the bigger batches -- and the
     // selection kernel's load schedule suffered from the second home of the distances: 4.0 against 2.6 ms per batch)
     const bool slim = fused && a.all_singleton && fused_counts_format(ctx, qb);
+    // a block whose queries hold bytes beyond ACGT- as gaps in its fp4 image (exotic_queries): its launches test through the
+    // loosened screen, k_query_exotic_fix follows each
+    const bool qfix = fused && a.all_singleton && qb.qx != nullptr && fused_counts_format(ctx, qb);
+    if (qfix && query_screen(ctx, qb.qx_top)) return 1;
     // the overlapped route applies (comment above; APPLES_EXOTIC_FIX_KERNEL, a diagnostic, puts a kernel that writes the batch's
-    // n_obs behind the GEMM: serial)
+    // n_obs behind the GEMM: serial -- and so does k_query_exotic_fix)
     const long long ovl_knob = knob(ctx, "APPLES_OVERLAP", -1);
-    const bool ovl_ok = slim && !cfused && !sfused && ctx->params.model == APPLES_JC69 && dist_gemm_usable(ctx) && a.L <= GEMM_MAX_L13 && !hybrid && !ctx->tree.scan &&
+    const bool ovl_ok = slim && !qfix && !cfused && !sfused && ctx->params.model == APPLES_JC69 && dist_gemm_usable(ctx) && a.L <= GEMM_MAX_L13 && !hybrid && !ctx->tree.scan &&
                         !knob_on(ctx, "APPLES_EXOTIC_FIX_KERNEL") && (ovl_knob < 0 ? OVERLAP_DEFAULT : ovl_knob != 0);
     if (ensure_workspace(ctx, a.n_refs, a.slots_pad, want, true, false, hybrid, fused, false, slim,
                          (cfused && !(ctx->dbg & APPLES_DBG_NO_CLUSTER_TOPUP)) ? a.reps_pad : 0,
@@ -2059,27 +2142,30 @@ int run_block_main(apples_ctx *ctx, QueryBlock &qb, const Feeder *feed) {
             else HIP_TRY(ctx, hipEventRecord(e[0], front));
             if (!ovl && fused_counts_format(ctx, qb))  // the matrix-core kernel writes only the non-empty segments' counts
                 HIP_TRY(ctx, hipMemsetAsync(w.seg_cnt, 0, (size_t)nq * (w.stride / 64) * sizeof(int32_t), front));
-            if (!ovl && launch_counts_fused(ctx, qb, q0, nh, dist_tile_for(ctx, nq), w.dist, w.seg_slot, w.seg_cnt)) return 1;
+            const int32_t *screen = qfix ? ctx->jc_mmax_q : nullptr;
+            if (!ovl && launch_counts_fused(ctx, qb, q0, nh, dist_tile_for(ctx, nq), w.dist, w.seg_slot, w.seg_cnt, screen)) return 1;
             if (!ovl && nh < nq) {  // the rest of the chunk travels meanwhile (split_feed: the GEMM form, packed survivors in seg_slot alone)
                 if (feed_rest(i)) return 1;
                 HIP_TRY(ctx, hipStreamWaitEvent(front, ctx->ev_feed[2 * i + 1], 0));
                 if (launch_counts_fused(ctx, qb, q0 + nh, nq - nh, dist_tile_for(ctx, nq), w.dist, w.seg_slot + nh * w.stride,
-                                        w.seg_cnt + nh * (w.stride / 64))) return 1;
+                                        w.seg_cnt + nh * (w.stride / 64), screen)) return 1;
                 ++launches;
             }
             // reference rows with bytes beyond ACGT- (the matrix-core pass took them for gaps): the survivors' exact counts
             // reference rows with bytes beyond ACGT- (the matrix-core pass took them for gaps): k_select_fast counts those sites for the
             // survivors on such rows and tests them once more (APPLES_EXOTIC_FIX_KERNEL: the same as a pass of its own, diagnostic)
-            const bool exfix = fused_counts_format(ctx, qb) && (a.ex_off != nullptr || ctx->jc_mmax_true != nullptr);
+            // (qfix: k_query_exotic_fix does that too, for every survivor of its loosened launch, beside the queries' own such bytes)
+            const bool exfix = !qfix && fused_counts_format(ctx, qb) && (a.ex_off != nullptr || ctx->jc_mmax_true != nullptr);
             const bool ex_kernel = knob_on(ctx, "APPLES_EXOTIC_FIX_KERNEL");
             if (exfix && ex_kernel && launch_exotic_fix(ctx, qb, q0, nq, w.seg_slot, w.seg_cnt, w.n_obs)) return 1;
+            if (qfix && launch_query_exotic_fix(ctx, qb, q0, nq, w.seg_slot, w.seg_cnt, w.n_obs)) return 1;
             if (!ovl) {
                 HIP_TRY(ctx, hipEventRecord(e[1], front));
                 ++launches;
             }
             SelectArgs sa = select_args_alignment(ctx, qb, q0);
             sa.seg_lut = fused_counts_format(ctx, qb) ? ctx->jc_lut : nullptr;
-            if (exfix && ex_kernel) sa.seg_surv = w.n_obs;  // (k_exotic_fix left the survivor counts where k_select_fast puts the observed counts)
+            if ((exfix && ex_kernel) || qfix) sa.seg_surv = w.n_obs;  // (k_exotic_fix / k_query_exotic_fix left the survivor counts where k_select_fast puts the observed counts)
             if (exfix && !ex_kernel) {
                 sa.ex_off = a.ex_off; sa.ex_site = a.ex_site; sa.ex_mmax = ctx->jc_mmax_true ? ctx->jc_mmax_true : ctx->jc_mmax;
                 sa.ex_all = ctx->jc_mmax_true ? 1 : 0; sa.q_raw = qb.raw + q0 * (int64_t)a.L; sa.L = a.L;
@@ -2415,6 +2501,8 @@ int apples_set_params(apples_ctx *ctx, const apples_params *params) {
             if (L >= GEMM_LONG_MIN_L) { bound_long.assign(65536, -1); std::copy(mmax.begin(), mmax.end(), bound_long.begin()); }
             dev_free(ctx->jc_mmax_true);
             ctx->jc_mmax_true = nullptr;
+            ctx->h_mmax = monotone ? mmax : std::vector<int32_t>();  // (the rule itself: query_screen loosens it for blocks with such bytes)
+            ctx->mmax_q_top = ctx->mmax_q_D = -1;
             if (monotone && ctx->aln.ex_max > 0) {
                 // reference rows with bytes beyond ACGT- (counted as gaps by the matrix-core pass): a pair's true counts are (valid + k,
                 // mism + k), 0 <= k <= ex_max, so the pass must keep (valid, mism) whenever SOME k passes: mmaxF[v] = max_k (mmax[v + k] - k).
@@ -2437,6 +2525,8 @@ int apples_set_params(apples_ctx *ctx, const apples_params *params) {
         dev_free(ctx->jc_mmax);
         ctx->jc_mmax = nullptr;
         ctx->gemm_thr = GemmThreshold();
+        ctx->h_mmax.clear();
+        ctx->mmax_q_top = ctx->mmax_q_D = -1;
     }
     // alignments beyond the 13-bit packed survivor word: the K-split pass's screen at the present -f / -V
     dev_free(ctx->jc_bound_long);
@@ -2503,7 +2593,7 @@ void apples_ctx_destroy(apples_ctx *ctx) {
     dev_free(a.raw); dev_free(a.d_slot_row); dev_free(a.packed); dev_free(a.ref_f4); dev_free(a.rep_f4); dev_free(a.rep_boff); dev_free(a.rep_loff); dev_free(a.loose_mp); dev_free(a.blk_rec_i); dev_free(a.blk_rec_e); dev_free(a.blk_rec_c); dev_free(a.blk_rec_p); dev_free(a.blk_pk_i); dev_free(a.blk_pk_e); dev_free(a.blk_stat[0]); dev_free(a.blk_stat[1]); dev_free(a.rep_soff); dev_free(a.cl_order); dev_free(a.mem_block); dev_free(a.blk_root); dev_free(a.blk_rslot); dev_free(a.blk_nodes); dev_free(a.e_of_slot); dev_free(a.e_of_blk); dev_free(a.e_node); dev_free(a.lvl_e); dev_free(a.rep_packed); dev_free(a.packed_rm); dev_free(a.aa_rep_idx); dev_free(a.aa_rep_mask); dev_free(a.aa_cm_idx); dev_free(a.aa_cm_mask); dev_free(a.aa_idx); dev_free(a.aa_mask); dev_free(a.sd_ref4); dev_free(a.sd_nvr); dev_free(a.aa_rows); dev_free(a.aa_mrows); dev_free(ctx->sd_tq4); dev_free(ctx->sd_list_img); dev_free(ctx->sd_list_ints); dev_free(a.slot_node); dev_free(a.slot_level); dev_free(a.lvl_slots);
     dev_free(a.slot_rep); dev_free(a.slot_mpos); dev_free(a.rep_slot); dev_free(a.rep_moff); dev_free(a.mem_slot);
     dev_free(a.rep_x); dev_free(a.rep_bad); dev_free(a.x_rm); dev_free(a.cl_xoff); dev_free(a.x_off); dev_free(a.x_rows);
-    dev_free(ctx->jc_lut); dev_free(ctx->jc_mmax); dev_free(ctx->jc_mmax_true); dev_free(ctx->jc_bound_long); dev_free(ctx->blosum); dev_free(ctx->d_col_perm); dev_free(ctx->d_col_node);
+    dev_free(ctx->jc_lut); dev_free(ctx->jc_mmax); dev_free(ctx->jc_mmax_true); dev_free(ctx->jc_mmax_q); dev_free(ctx->jc_bound_long); dev_free(ctx->blosum); dev_free(ctx->d_col_perm); dev_free(ctx->d_col_node);
     dev_free(ctx->d_col_level);
     for (int i = 0; i < 8; ++i)
         if (ctx->ev[i]) (void)hipEventDestroy(ctx->ev[i]);
@@ -2596,10 +2686,11 @@ int apples_place_sequences_streamed(apples_ctx *ctx, const uint8_t *queries, int
     if (!rc && ctx->params.model != APPLES_SCOREDIST) rc = take_exotic(ctx, ctx->stream2, &exotic);
     if (!rc && exotic && planes == 2 && ctx->aln.ex_ok) {
         // a query carried a symbol beyond ACGT-, which the pass took for a gap: those queries once more through the 8-plane
-        // kernels (a few: a block of their own; many: the whole block) -- the context keeps its matrix-core forms
+        // kernels (a few: a block of their own; many: the whole block, exotic_queries) -- the context keeps its matrix-core forms
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         rc = exotic_queries(ctx, &qb, queries, self_row);
-        if (!rc) rc = qb.exact8 ? run_block(ctx, qb) : run_ex_block(ctx, qb);
+        // (many of them: the whole block once more, through the matrix-core pass with k_query_exotic_fix behind it where that route applies)
+        if (!rc) rc = (qb.exact8 || qb.qx) ? run_block(ctx, qb) : run_ex_block(ctx, qb);
     } else if (!rc && exotic && planes == 2) {
         // a query carried a symbol beyond ACGT-: the 2-plane images are not valid for it.  Rare: widen
         // the reference to raw bytes and run the block again from a whole-block upload
@@ -3088,7 +3179,7 @@ const char *apples_describe(apples_ctx *ctx) {
              "\"scoredist_filter\": %d, \"scoredist_image_bytes\": %lld, \"cluster_blocks\": %d, \"block_items_last_batch\": %d, \"block_tiles_last_batch\": %d, "
              "\"exotic_symbols_as_gaps\": %d, \"exotic_sites_max_per_row\": %d, \"eight_plane_copy\": %d, \"cluster_exotic_clusters\": %d, "
              "\"ragged_rows\": %d, \"row_small\": %lld, \"big_rows\": %lld, \"big_rows_last_batch\": %d, \"full_rows_for_good\": %d, "
-             "\"overlap\": %d, \"overlap_batches\": %d}",
+             "\"overlap\": %d, \"overlap_batches\": %d, \"query_exotic_fixes\": %lld, \"query_exotic_loosened_by\": %lld}",
              name, cus, ctx->tree.n_nodes, ctx->tree.height, ctx->tree.max_children, (long long)a.n_rows, (long long)a.n_refs,
              (long long)a.n_reps, a.L, a.planes, a.all_singleton ? 1 : 0,
              (long long)((int64_t)a.G * (a.planes + 1) * a.slots_pad * 16), (long long)ctx->ws.batch, ctx->ws.small.wgs,
@@ -3122,7 +3213,9 @@ const char *apples_describe(apples_ctx *ctx) {
              a.ex_ok ? 1 : 0, (int)a.ex_max, a.packed8 ? 1 : 0, (int)a.n_xclusters,
              ctx->ws.ragged ? 1 : 0, (long long)ctx->ws.row_small, (long long)ctx->ws.row_big, (int)big_used, ctx->no_ragged ? 1 : 0,
              // the last block's pass: distance GEMM of batch b + 1 beside selection and sweep of batch b (run_block_main); its device batches
-             ctx->overlap, ctx->overlap_batches);
+             ctx->overlap, ctx->overlap_batches,
+             // launches of k_query_exotic_fix (query blocks with bytes beyond ACGT- on the matrix-core pass: exotic_queries), the D of the last
+             (long long)ctx->query_exotic_fixes, (long long)ctx->query_exotic_D);
     ctx->desc = buf;
     return ctx->desc.c_str();
 }

@@ -234,6 +234,12 @@ struct QueryBlock {
     bool exact8 = false;          // the block's fused pass runs on the 8-plane forms (its queries carry such bytes): no matrix cores
     QueryBlock *ex_block = nullptr;  // the block's few queries with such bytes once more as an exact8 block of their own ...
     int32_t *ex_idx = nullptr;       // ... and which queries they are [ex_block->n] (run_block places them last and copies the structs over)
+    // ... or, many of them in a singleton context of fewer than 8 192 sites: the block STAYS on the matrix-core pass (its fp4 image
+    // holds such bytes as gaps), the pass's screen is loosened for its launches and dist.hip: k_query_exotic_fix gives every survivor
+    // its exact counts (api.hip: exotic_queries)
+    uint4 *qx = nullptr;          // [flagged queries][G] mask planes, bit = the site holds such a byte (the gap plane's bit order); non-null: this route
+    int32_t *qx_idx = nullptr;    // [n_pad] index of the query's plane in qx, -1: a clean query
+    int32_t qx_top = 0;           // most such bytes in one query that takes the route (the screen is loosened by it: apples_ctx::jc_mmax_q)
     uint8_t *qf4 = nullptr;       // fp4 operand image for the matrix-core distance kernels: [n_pad128][2G][4][32 B] (t1, t2, t3, v) for
                                   // k_jc69_mfma; beside a reference or representative image (DevAlign::ref_f4 / rep_f4) the compact tiled form of dist_gemm.hip
     uint8_t *aa_idx = nullptr;    // [n_pad][Lpad16] residue index (20 = gap)
@@ -357,6 +363,15 @@ struct apples_ctx {
     int32_t *jc_mmax = nullptr;  // [L+1] largest mismatch count with 0 <= lut <= threshold, per valid count
     int32_t *jc_mmax_true = nullptr;  // jc_mmax is the FILTER's table where the reference holds bytes beyond ACGT- (a pair's counts may still
                                       // grow by up to ex_max: set_params); this is the rule itself, what k_exotic_fix tests.  nullptr: jc_mmax is
+    // Query blocks whose queries hold bytes beyond ACGT- as gaps in their fp4 image (QueryBlock::qx): a pair's true counts are
+    // (valid + t, mism + t - j), t <= ex_max + the query's such bytes, j <= D matching sites where both hold the same such byte.  The
+    // screen of THEIR launches: jc_mmax_q[v] = max over t of (rule[v + t] - t) + D, built with the first such block (api.hip:
+    // query_screen) and rebuilt when a block asks for more; launches over clean blocks keep jc_mmax / gemm_thr.
+    std::vector<int32_t> h_mmax;       // the rule's own table on the host (what jc_mmax_true, or else jc_mmax, holds)
+    int32_t *jc_mmax_q = nullptr;      // [L + 1]
+    int64_t mmax_q_top = -1, mmax_q_D = -1;  // what jc_mmax_q was built for: such bytes per query at most, D (-1: not built)
+    int64_t query_exotic_fixes = 0;    // launches of k_query_exotic_fix (describe(): "query_exotic_fixes")
+    int64_t query_exotic_D = 0;        // D of the last such launch (describe(): "query_exotic_loosened_by")
     int32_t *jc_bound_long = nullptr;  // [65 536] (the kernel indexes with a 16-bit count; -1 beyond L) the K-split pass's integer screen, a
                                        // superset of the rule.  Without a distance table: -1 where the overlap rule excludes the valid
                                        // count, else min(valid, m* + 1), m* = the largest mismatch count the host's log lets pass
@@ -437,6 +452,8 @@ int launch_pack_aa(apples_ctx *ctx, const uint8_t *d_raw, int64_t n_rows, int L,
 int launch_pack_exotic_masks(apples_ctx *ctx, const int32_t *d_cl_xoff, uint4 *d_x_rm, uint4 *d_rep_x);
 // ... one plane per flagged slot (DevAlign::x_off / x_rows); d_x_cnt[x_off[slot]] += the slot's such sites (the caller zeroes it)
 int launch_pack_exotic_mask_rows(apples_ctx *ctx, const int32_t *d_x_off, uint4 *d_x_rows, int32_t *d_x_cnt);
+// the same for the n rows of a query block (d_raw: its rows back to back; d_idx: per query the index of its plane in d_planes, -1: clean)
+int launch_pack_query_masks(apples_ctx *ctx, const uint8_t *d_raw, int64_t n, const int32_t *d_idx, uint4 *d_planes, int32_t *d_cnt);
 // dist.hip
 int launch_counts(apples_ctx *ctx, const QueryBlock &qb, int64_t q0, int64_t nq, int tile, double *d_dist,
                   uint32_t *d_counts);
@@ -604,7 +621,10 @@ int launch_expand_queries_f4(apples_ctx *ctx, const uint8_t *d_raw, int64_t n, u
 // dist_gemm.hip
 bool dist_gemm_usable(const apples_ctx *ctx);
 // (share: the form of one four-wavefront workgroup per CU, which leaves half of every CU's registers to a kernel beside it)
-int launch_counts_gemm(apples_ctx *ctx, const QueryBlock &qb, int64_t q0, int64_t nq, int32_t *seg_slot, int32_t *seg_cnt, bool share = false);
+// (screen: the launch tests through this table in place of the context's threshold -- apples_ctx::jc_mmax_q for a block that holds bytes
+// beyond ACGT- as gaps; nullptr: the context's)
+int launch_counts_gemm(apples_ctx *ctx, const QueryBlock &qb, int64_t q0, int64_t nq, int32_t *seg_slot, int32_t *seg_cnt, bool share = false,
+                       const int32_t *screen = nullptr);
 // k_jc69_gemm_long: the fused pass of 2-plane blocks on alignments of GEMM_LONG_MIN_L sites and more; writes k_jc69 MODE 1's format
 bool dist_gemm_long_usable(const apples_ctx *ctx);
 // (image / rows: the reference-side operand image and its padded row count -- DevAlign::ref_f4 and slots_pad by default, the
@@ -614,7 +634,7 @@ int launch_counts_gemm_long(apples_ctx *ctx, const QueryBlock &qb, int64_t q0, i
 // the context keeps compact, tiled fp4 images (a reference or a representative image exists): the query blocks' qf4 are then compact too
 inline bool f4_images_compact(const apples_ctx *ctx) { return ctx->aln.ref_f4 != nullptr || ctx->aln.rep_f4 != nullptr; }
 int launch_counts_fused(apples_ctx *ctx, const QueryBlock &qb, int64_t q0, int64_t nq, int tile, double *seg_d,
-                        int32_t *seg_slot, int32_t *seg_cnt);
+                        int32_t *seg_slot, int32_t *seg_cnt, const int32_t *screen = nullptr);
 int launch_counts_listed(apples_ctx *ctx, const QueryBlock &qb, int64_t q0, int64_t nq_max, const int32_t *qlist,
                          const int32_t *qcount, double *d_dist, double *segmin_d, int32_t *segmin_i);
 // the fused matrix-core pass's survivors (packed words in seg_slot) on reference rows with bytes beyond ACGT-: exact counts, the
@@ -626,6 +646,10 @@ int launch_long_exotic_fix(apples_ctx *ctx, const QueryBlock &qb, int64_t q0, in
                            int32_t *seg_cnt, const int32_t *row_off, const uint4 *masks, int64_t rows);
 int launch_exotic_fix(apples_ctx *ctx, const QueryBlock &qb, int64_t q0, int64_t nq, int32_t *seg_slot, const int32_t *seg_cnt,
                       int32_t *n_surv);  // (diagnostic form: api.hip does the same inside k_select_fast)
+// ... and behind a loosened launch over a block whose QUERIES hold such bytes (QueryBlock::qx): every survivor's exact counts from the
+// query's mask plane, the row's letter plane and the row's site list, the rule's own table, n_surv as above (replaces k_exotic_fix there)
+int launch_query_exotic_fix(apples_ctx *ctx, const QueryBlock &qb, int64_t q0, int64_t nq, int32_t *seg_slot, const int32_t *seg_cnt,
+                            int32_t *n_surv);
 bool exact8_rows(const apples_ctx *ctx, const QueryBlock &qb);  // the bit-plane kernels take the 8-plane forms for this block
 // sweep.hip
 struct SweepArgs {

@@ -536,14 +536,14 @@ int launch_expand_queries_f4(apples_ctx *ctx, const uint8_t *d_raw, int64_t n, u
 
 template <int MODE>
 static int launch_mfma(apples_ctx *ctx, const QueryBlock &qb, int64_t q0, int64_t nq, double *d_dist, uint32_t *d_counts,
-                       int32_t *seg_slot, int32_t *seg_cnt) {
+                       int32_t *seg_slot, int32_t *seg_cnt, const int32_t *screen = nullptr) {
     const DevAlign &a = ctx->aln;
     const bool no_mmax = knob_on(ctx, "APPLES_NO_MMAX");
     dim3 grid((unsigned)(a.slots_pad / 128), (unsigned)((nq + MF_QT - 1) / MF_QT));
     hipLaunchKernelGGL((k_jc69_mfma<MODE>), grid, dim3(MF_TPB), 0, ctx->stream, a.packed,
                        qb.qf4 + q0 * (int64_t)a.G * 256, d_dist, d_counts, a.n_rows, a.slots_pad, a.G, nq, a.L,
                        ctx->params.overlap_frac, ctx->jc_lut, ctx->params.filt_threshold, seg_slot, seg_cnt,
-                       no_mmax ? nullptr : ctx->jc_mmax);
+                       no_mmax ? nullptr : (screen ? screen : ctx->jc_mmax));
     HIP_TRY(ctx, hipGetLastError());
     return 0;
 }
@@ -621,12 +621,13 @@ int launch_counts(apples_ctx *ctx, const QueryBlock &qb, int64_t q0, int64_t nq,
 }
 
 // fused threshold compaction (MODE 1): see k_select_fast for the consumer
+// (screen: the table a launch over a block with bytes beyond ACGT- in its queries tests through -- apples_ctx::jc_mmax_q; the matrix-core forms only)
 int launch_counts_fused(apples_ctx *ctx, const QueryBlock &qb, int64_t q0, int64_t nq, int tile, double *seg_d,
-                        int32_t *seg_slot, int32_t *seg_cnt) {
+                        int32_t *seg_slot, int32_t *seg_cnt, const int32_t *screen) {
     if (nq == 0) return 0;
     if (fused_counts_format(ctx, qb))
-        return dist_gemm_usable(ctx) ? launch_counts_gemm(ctx, qb, q0, nq, seg_slot, seg_cnt)
-                                     : launch_mfma<1>(ctx, qb, q0, nq, seg_d, nullptr, seg_slot, seg_cnt);
+        return dist_gemm_usable(ctx) ? launch_counts_gemm(ctx, qb, q0, nq, seg_slot, seg_cnt, false, screen)
+                                     : launch_mfma<1>(ctx, qb, q0, nq, seg_d, nullptr, seg_slot, seg_cnt, screen);
     // alignments of GEMM_LONG_MIN_L sites and more, ACGT- blocks: the K-split GEMM writes the format of k_jc69 MODE 1
     // (a context whose reference rows hold bytes beyond ACGT- -- DevAlign::x_off; its blocks carry 8-plane copies for the full rows,
     // which is not what keeps a block off this route: QueryBlock::exact8 is -- runs the kernel's EX form and completes the counts behind it)
@@ -1057,6 +1058,112 @@ int launch_long_exotic_fix(apples_ctx *ctx, const QueryBlock &qb, int64_t q0, in
                        qb.packed, q0, a.G, a.L, row_off, masks, ctx->params.overlap_frac, ctx->params.filt_threshold, ctx->jc_lut);
     HIP_TRY(ctx, hipGetLastError());
     ++ctx->long_exotic_fixes;
+    return 0;
+}
+
+// ---- bytes beyond ACGT- in the QUERIES of a block that stays on the matrix-core pass (QueryBlock::qx; api.hip: exotic_queries) ------
+// The block's fp4 image holds such bytes as gaps, as the reference's forms do, so the pass counted the letter-against-letter
+// sites (v, m) alone.  With M = a row's letter plane and X = its plane of such bytes, a pair's counts by apples/distance.py:733-737 are
+//   valid = v + k1 + k2 + k3,  mism = m + k1 + k2 + k3x
+//   k1 = popc(Xq & Mr)  such a byte in the query under a letter of the row: valid, the bytes differ
+//   k2 = popc(Mq & Xr)  the reverse (k_exotic_fix's term)
+//   k3 = popc(Xq & Xr)  such bytes in both: valid, and k3x of them differ (N against N is a match)
+// The k3 - k3x matching sites LOWER the distance: the launch's screen was loosened by D of them (apples_ctx::jc_mmax_q), so its
+// survivors are a superset again, and every one of them is tested here on the integers against the rule's own table.
+//
+// One workgroup per query.  It stages the query's X plane (G <= 64 words of 16 bytes) and raw row (at most 8 191 bytes) in LDS.
+// Its wavefronts deal the query's segments among themselves 64 at a time as k_long_exotic_fix does: one read brings 64 counts, a
+// ballot names the live ones, and in a live segment lane e owns survivor e.  k1: a loop over the word groups -- every lane reads
+// the letter plane word of its own row ([g][plane 0][slot]: the lanes of a segment read inside one contiguous kilobyte) and ANDs it
+// with the staged word, a broadcast read.  k2, k3: the row's site list walked against the staged query row -- a letter there:
+// (+1, +1); such a byte there: (+1, + whether it differs from the row's raw byte); a gap: nothing.  Then the word is rewritten, or
+// its valid field zeroed (the table says -1 there: k_select_fast with SelectArgs::seg_surv drops it), and the query's number of
+// survivors goes to n_surv: k_exotic_fix's contract.  Padding slots (all-gap rows the loosened screen may let through) are dropped.
+namespace {
+__global__ __launch_bounds__(APPLES_TPB) void k_query_exotic_fix(int32_t *__restrict__ seg_slot, const int32_t *__restrict__ seg_cnt, int64_t stride,
+                                                                int64_t n_rows, const uint8_t *__restrict__ qraw, int L, int G,
+                                                                const int32_t *__restrict__ qx_idx, const uint4 *__restrict__ qx,
+                                                                const uint4 *__restrict__ packed, const int32_t *__restrict__ ex_off,
+                                                                const uint16_t *__restrict__ ex_site, const uint8_t *__restrict__ ref_raw,
+                                                                const int32_t *__restrict__ slot_row, const int32_t *__restrict__ mmax,
+                                                                int32_t *__restrict__ n_surv) {
+    __shared__ uint4 xq[64];         // the query's plane of such bytes (L < 8192: G <= 64)
+    __shared__ uint8_t qrow[8192];   // its raw row
+    __shared__ int sh_cnt[APPLES_TPB / WAVE];
+    const int64_t q = blockIdx.x;
+    const int xi = qx_idx[q];
+    if (xi >= 0)
+        for (int g = threadIdx.x; g < G; g += APPLES_TPB) xq[g] = qx[(int64_t)xi * G + g];
+    if (xi >= 0 || ex_off) {
+        const uint8_t *src = qraw + q * (int64_t)L;
+        for (int i = threadIdx.x; i < L; i += APPLES_TPB) qrow[i] = src[i];
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
+    const int64_t n_seg = stride >> 6;
+    const int32_t *cnt_q = seg_cnt + q * n_seg;
+    int kept = 0;
+    for (int64_t s0 = (int64_t)wv * WAVE; s0 < n_seg; s0 += APPLES_TPB) {  // 64 segments per wavefront and trip
+        const int c_mine = s0 + lane < n_seg ? cnt_q[s0 + lane] : 0;
+        for (unsigned long long live = __ballot(c_mine > 0); live; live &= live - 1) {
+            const int sl = __builtin_ctzll(live);
+            const int c = __builtin_amdgcn_readlane(c_mine, sl);
+            if (lane < c) {
+                int32_t *w = seg_slot + q * stride + (s0 + sl) * 64 + lane;
+                const uint32_t pk = (uint32_t)*w;
+                const int64_t slot = (s0 + sl) * 64 + (pk >> 26);
+                int valid = (int)((pk >> 13) & 0x1fffu), mism = (int)(pk & 0x1fffu);
+                bool ok = slot < n_rows;
+                if (ok && xi >= 0) {  // k1
+                    int k1 = 0;
+                    for (int g = 0; g < G; ++g) {
+                        const uint4 m = packed[(int64_t)g * 3 * stride + slot], x = xq[g];
+                        k1 += __popc(m.x & x.x) + __popc(m.y & x.y) + __popc(m.z & x.z) + __popc(m.w & x.w);
+                    }
+                    valid += k1; mism += k1;
+                }
+                if (ok && ex_off) {  // k2, k3
+                    const int e0 = ex_off[slot], e1 = ex_off[slot + 1];
+                    const uint8_t *rrow = e1 > e0 ? ref_raw + (int64_t)slot_row[slot] * L : nullptr;
+                    for (int e = e0; e < e1; ++e) {
+                        const int site = ex_site[e];
+                        const uint8_t b = qrow[site];
+                        if (b == '-') continue;
+                        ++valid;
+                        mism += b != rrow[site] ? 1 : 0;  // (a letter differs from the row's byte as it is)
+                    }
+                }
+                ok = ok && mism <= mmax[valid];
+                *w = (int32_t)(ok ? ((pk & 0xfc000000u) | ((uint32_t)valid << 13) | (uint32_t)mism) : (pk & 0xfc000000u));
+                kept += ok ? 1 : 0;
+            }
+        }
+    }
+    for (int o = WAVE / 2; o > 0; o >>= 1) kept += __shfl_down(kept, o, WAVE);
+    if (lane == 0) sh_cnt[wv] = kept;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int t = 0;
+        for (int i = 0; i < APPLES_TPB / WAVE; ++i) t += sh_cnt[i];
+        n_surv[q] = t;
+    }
+}
+}  // namespace
+
+int launch_query_exotic_fix(apples_ctx *ctx, const QueryBlock &qb, int64_t q0, int64_t nq, int32_t *seg_slot, const int32_t *seg_cnt,
+                            int32_t *n_surv) {
+    if (nq == 0) return 0;
+    const DevAlign &a = ctx->aln;
+    if (!qb.qx || !qb.qx_idx || a.planes != 2 || a.G > 64 || a.L >= 8192 || (a.ex_off && !a.d_slot_row)) {
+        ctx->err = "k_query_exotic_fix: needs a block with mask planes in a 2-plane context of fewer than 8 192 sites";
+        return 1;
+    }
+    hipLaunchKernelGGL(k_query_exotic_fix, dim3((unsigned)nq), dim3(APPLES_TPB), 0, ctx->stream, seg_slot, seg_cnt, a.slots_pad, a.n_rows,
+                       qb.raw + q0 * (int64_t)a.L, a.L, a.G, qb.qx_idx + q0, qb.qx, a.packed, a.ex_off, a.ex_site, a.raw, a.d_slot_row,
+                       ctx->jc_mmax_true ? ctx->jc_mmax_true : ctx->jc_mmax, n_surv);
+    HIP_TRY(ctx, hipGetLastError());
+    ++ctx->query_exotic_fixes;
+    ctx->query_exotic_D = ctx->mmax_q_D;
     return 0;
 }
 

@@ -418,7 +418,10 @@ bool dist_gemm_usable(const apples_ctx *ctx) {
 // registers.  The kernel's 72 / 80 KB of LDS would let a CU take two, and a grid of one per CU would then sit two deep on half the
 // chip; dynamic LDS (unused) lifts the workgroup above half a CU's 160 KB, so that the second one cannot land beside the first.
 // Counts and output format are the QT = 256 form's, bit for bit (same decode, same compaction; the tile order differs).
-int launch_counts_gemm(apples_ctx *ctx, const QueryBlock &qb, int64_t q0, int64_t nq, int32_t *seg_slot, int32_t *seg_cnt, bool share) {
+// `screen`: the launch tests through this table (the table form) in place of the context's threshold: a block whose queries hold bytes
+// beyond ACGT- as gaps (apples_ctx::jc_mmax_q).  Launches without one are what they were.
+int launch_counts_gemm(apples_ctx *ctx, const QueryBlock &qb, int64_t q0, int64_t nq, int32_t *seg_slot, int32_t *seg_cnt, bool share,
+                       const int32_t *screen) {
     const DevAlign &a = ctx->aln;
     // tuning knob: 128 = two four-wavefront workgroups per CU (measured at C3: 30.8 ms against 29.4 -- what the second
     // workgroup hides of the first one's epilogue and barrier stalls costs more in DMA traffic)
@@ -434,7 +437,8 @@ int launch_counts_gemm(apples_ctx *ctx, const QueryBlock &qb, int64_t q0, int64_
     }
     const int64_t grid = std::max(8, ctx->n_cu / 8 * 8) * (share ? 1 : 256 / QT);
     const bool table = knob_on(ctx, "APPLES_GEMM_TABLE");  // diagnostic knob: threshold through the LDS table
-    const bool lin = ctx->gemm_thr.ok && !table;
+    const bool lin = ctx->gemm_thr.ok && !table && !screen;
+    const int32_t *mmax = screen ? screen : ctx->jc_mmax;
     const int R = (a.G * 2 - 2) % 3;
     // (static LDS of the QT = 128 forms: three generations of 24 KB, and the table where the threshold goes through it)
     const bool tab12 = a.L > GEMM_MAX_L13;
@@ -443,7 +447,7 @@ int launch_counts_gemm(apples_ctx *ctx, const QueryBlock &qb, int64_t q0, int64_
     if (tab12) {  // 2 047 .. 4 092 sites: the validity sum at 2^12, integer decode, the threshold through the table
 #define GM_LAUNCH12(R_, QT_)                                                                                         \
     hipLaunchKernelGGL((k_jc69_gemm<false, R_, QT_, 12>), dim3((unsigned)grid), dim3(QT_ * 2), dyn, ctx->stream, a.ref_f4, \
-                       qb.qf4, q0, a.slots_pad, a.G * 2, nq, a.L, TQ, TR, seg_slot, seg_cnt, ctx->jc_mmax, ctx->gemm_thr)
+                       qb.qf4, q0, a.slots_pad, a.G * 2, nq, a.L, TQ, TR, seg_slot, seg_cnt, mmax, ctx->gemm_thr)
         if (QT == 256) { if (R == 0) GM_LAUNCH12(0, 256); else if (R == 1) GM_LAUNCH12(1, 256); else GM_LAUNCH12(2, 256); }
         else { if (R == 0) GM_LAUNCH12(0, 128); else if (R == 1) GM_LAUNCH12(1, 128); else GM_LAUNCH12(2, 128); }
 #undef GM_LAUNCH12
@@ -453,7 +457,7 @@ int launch_counts_gemm(apples_ctx *ctx, const QueryBlock &qb, int64_t q0, int64_
 #define GM_LAUNCH(LIN_, R_, QT_)                                                                                     \
     hipLaunchKernelGGL((k_jc69_gemm<LIN_, R_, QT_>), dim3((unsigned)grid), dim3(QT_ * 2), dyn, ctx->stream, a.ref_f4,  \
                        qb.qf4, q0, a.slots_pad, a.G * 2, nq, a.L, TQ, TR, seg_slot, seg_cnt,                         \
-                       ctx->jc_mmax, ctx->gemm_thr)
+                       mmax, ctx->gemm_thr)
 #define GM_LAUNCH_R(LIN_, QT_)                                                                                       \
     do { if (R == 0) GM_LAUNCH(LIN_, 0, QT_); else if (R == 1) GM_LAUNCH(LIN_, 1, QT_); else GM_LAUNCH(LIN_, 2, QT_); } while (0)
     if (QT == 256) { if (lin) GM_LAUNCH_R(true, 256); else GM_LAUNCH_R(false, 256); }

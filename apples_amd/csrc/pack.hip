@@ -239,7 +239,7 @@ __global__ __launch_bounds__(APPLES_TPB) void k_pack_exotic_mask_rows(const uint
     const int xo = slot < n_rows ? x_off[slot] : -1;
     uint32_t x = 0;
     if (xo >= 0 && w * 32 < L) {
-        const uint8_t *src = raw + (int64_t)slot_row[slot] * L + w * 32;
+        const uint8_t *src = raw + (slot_row ? (int64_t)slot_row[slot] : slot) * L + w * 32;  // (no map: the rows of a query block, in order)
         const int nb = min(32, L - w * 32);
         for (int i = 0; i < nb; ++i) {
             const uint32_t b = src[i];
@@ -261,6 +261,18 @@ int launch_pack_exotic_mask_rows(apples_ctx *ctx, const int32_t *d_x_off, uint4 
     if (total == 0) return 0;
     hipLaunchKernelGGL(k_pack_exotic_mask_rows, dim3((unsigned)((total + APPLES_TPB - 1) / APPLES_TPB)), dim3(APPLES_TPB), 0, ctx->stream,
                        a.raw, a.L, a.G, a.n_rows, a.d_slot_row, d_x_off, d_x_rows, d_x_cnt);
+    HIP_TRY(ctx, hipGetLastError());
+    return 0;
+}
+
+// ... and for the queries of a block that stays on the matrix-core pass with such bytes as gaps (QueryBlock::qx; dist.hip:
+// k_query_exotic_fix): one plane per flagged query, query-major, and the query's number of such bytes in d_cnt[its plane]
+int launch_pack_query_masks(apples_ctx *ctx, const uint8_t *d_raw, int64_t n, const int32_t *d_idx, uint4 *d_planes, int32_t *d_cnt) {
+    const DevAlign &a = ctx->aln;
+    const int64_t total = n * (int64_t)a.G * 4;
+    if (total == 0) return 0;
+    hipLaunchKernelGGL(k_pack_exotic_mask_rows, dim3((unsigned)((total + APPLES_TPB - 1) / APPLES_TPB)), dim3(APPLES_TPB), 0, ctx->stream,
+                       d_raw, a.L, a.G, n, (const int32_t *)nullptr, d_idx, d_planes, d_cnt);
     HIP_TRY(ctx, hipGetLastError());
     return 0;
 }
