@@ -662,8 +662,29 @@ int setup_alignment(apples_ctx *ctx, const apples_tree *t, const apples_alignmen
         // (decided below, once the rows are packed: a clean reference keeps today's rule and widens with the first such query):
         // one mask plane per flagged slot (DevAlign::x_off / x_rows) and k_long_exotic_fix behind the pass
         const bool ex_long = a.all_singleton && a.L >= GEMM_LONG_MIN_L && dist_mfma_enabled(ctx) && !(ctx->dbg & APPLES_DBG_NO_DIST_GEMM);
-        a.ex_ok = ((a.all_singleton || cl_ex) && dist_mfma_enabled(ctx) && a.L < 8192) || ex_long;
+        // ... and in a clustered context of these lengths on the long forms of the fused route (the panels' conditions below with
+        // cl_long): the panels' mask planes as at short lengths, the flagged representatives' once more representative-major for
+        // k_long_exotic_fix behind their K-split pass (DevAlign::rep_xoff / rep_xrows).  Clean or not, such a context keeps its
+        // 2-plane forms when a query block brings such bytes (exotic_queries)
+        const bool cl_ex_long = cl_ex && a.L >= GEMM_LONG_MIN_L && dist_mfma_enabled(ctx) && !(ctx->dbg & APPLES_DBG_NO_DIST_GEMM);
+        a.ex_ok = ((a.all_singleton || cl_ex) && dist_mfma_enabled(ctx) && a.L < 8192) || ex_long || cl_ex_long;
         std::vector<int32_t> cl_bad;  // clustered: the flagged slots
+        // (cl_ex_long) the bytes beyond ACGT- of the slots marked in `map`, counted on the device -- rows of these lengths hold hundreds
+        // of them, no site lists -- and, with `planes`, their mask planes slot-major.  map[s] becomes the slot's index among the marked
+        // or -1; returns the most such bytes in one row, -1 on failure
+        auto mask_rows = [&](std::vector<int32_t> &map, uint4 **planes) -> int32_t {
+            int32_t n_x = 0, *d_map = nullptr, *d_cnt = nullptr;
+            for (int64_t s = 0; s < a.slots_pad; ++s) map[s] = (s < a.n_rows && map[s]) ? n_x++ : -1;
+            std::vector<int32_t> cnt((size_t)std::max(n_x, 1), 0);
+            int bad = (planes && dev_alloc(ctx, planes, (int64_t)n_x * a.G)) || dev_upload(ctx, &d_map, map.data(), a.slots_pad) ||
+                      dev_upload(ctx, &d_cnt, cnt.data(), (int64_t)cnt.size()) ||
+                      launch_pack_exotic_mask_rows(ctx, d_map, planes ? *planes : nullptr, d_cnt) ||
+                      hipMemcpyAsync(cnt.data(), d_cnt, cnt.size() * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+                      hipStreamSynchronize(ctx->stream) != hipSuccess;  // (the vectors are the caller's and locals)
+            dev_free(d_map); dev_free(d_cnt);
+            if (bad) { if (ctx->err.empty()) ctx->err = "mask planes of the rows with bytes beyond ACGT-: failed"; return -1; }
+            return *std::max_element(cnt.begin(), cnt.end());
+        };
         int32_t *d_row_bad = nullptr;
         if (a.ex_ok) {
             if (dev_alloc(ctx, &d_row_bad, a.slots_pad)) return 1;
@@ -695,6 +716,14 @@ int setup_alignment(apples_ctx *ctx, const apples_tree *t, const apples_alignmen
             exotic = 0;
         } else if (ex_long) {
             a.ex_ok = false;  // a clean reference of these lengths: nothing kept beside the 2-plane rows
+        } else if (exotic && cl_ex_long) {
+            // which slots (the mask planes come with the panels, below), the most such bytes of a row, and the 8-plane form
+            std::vector<int32_t> bad((size_t)a.slots_pad, 0);
+            HIP_TRY(ctx, hipMemcpy(bad.data(), d_row_bad, (size_t)a.n_rows * sizeof(int32_t), hipMemcpyDeviceToHost));
+            cl_bad = bad;
+            if ((a.ex_max = mask_rows(bad, nullptr)) < 0) return 1;
+            if (ensure_packed8(ctx)) return 1;
+            exotic = 0;
         } else if (exotic && a.ex_ok) {
             // which slots, which sites (from the caller's rows: only the flagged rows are read again), and the 8-plane form
             std::vector<int32_t> bad((size_t)a.n_rows), off((size_t)a.n_rows + 1, 0);
@@ -760,6 +789,7 @@ int setup_alignment(apples_ctx *ctx, const apples_tree *t, const apples_alignmen
                     bool flagged = false;
                     for (int m = rep_moff[j]; m < rep_moff[j + 1] && !flagged; ++m) flagged = cl_bad[mem_slot[m]] != 0;
                     if (flagged) {
+                        if (words > INT32_MAX) { ctx->err = "mask planes of the clusters with bytes beyond ACGT-: more than 2^31 words"; return 1; }
                         xoff[j] = (int32_t)words;
                         words += (int64_t)a.G * (rep_moff[j + 1] - rep_moff[j]);
                         ++a.n_xclusters;
@@ -776,6 +806,18 @@ int setup_alignment(apples_ctx *ctx, const apples_tree *t, const apples_alignmen
                 }
                 if (launch_pack_exotic_masks(ctx, a.cl_xoff, a.x_rm, a.rep_x)) return 1;
                 HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (the vectors are locals)
+                if (cl_long && any_rep) {
+                    // the long route's pass over the representatives' image: the flagged ones' planes once more, one after the other
+                    // (k_long_exotic_fix reads a row's plane in whole kilobytes), addressed by representative index; their most such
+                    // bytes is what set_params loosens that pass's screen by
+                    std::vector<int32_t> map((size_t)a.slots_pad, 0), rxoff((size_t)a.reps_pad, -1);
+                    for (int64_t j = 0; j < a.n_reps; ++j)
+                        if (rbad[j]) map[rep_slot[j]] = 1;
+                    if ((a.rep_ex_max = mask_rows(map, &a.rep_xrows)) < 0) return 1;
+                    for (int64_t j = 0; j < a.n_reps; ++j) rxoff[j] = map[rep_slot[j]];
+                    if (dev_upload(ctx, &a.rep_xoff, rxoff.data(), a.reps_pad)) return 1;
+                    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+                }
             }
             if (cl_long) {
                 // the representatives' rows once more as a compact fp4 image in representative order (k_jc69_gemm_long's reference
@@ -1942,6 +1984,10 @@ int run_block_main(apples_ctx *ctx, QueryBlock &qb, const Feeder *feed) {
                 // (both write every segment's count)
                 if (csd ? launch_scoredist_reps(ctx, qb, q0, nq, ctx->sd_rep_d, w.seg_slot, w.seg_cnt)
                         : launch_counts_gemm_long(ctx, qb, q0, nq, ctx->sd_rep_d, w.seg_slot, w.seg_cnt, a.rep_f4, a.reps_pad)) return 1;
+                // representatives with bytes beyond ACGT- (the image holds them as gaps): the pass stopped at its loosened screen and
+                // left packed totals; the true counts and the exact test, the segments closed up in place
+                if (cl_long && a.rep_xoff &&
+                    launch_long_exotic_fix(ctx, qb, q0, nq, ctx->sd_rep_d, w.seg_slot, w.seg_cnt, a.rep_xoff, a.rep_xrows, a.reps_pad)) return 1;
             } else {
                 HIP_TRY(ctx, hipMemsetAsync(w.seg_cnt, 0, (size_t)nq * (a.reps_pad / 64) * sizeof(int32_t), front));
                 if (launch_counts_reps(ctx, qb, q0, nq, w.seg_slot, w.seg_cnt)) return 1;
@@ -1962,9 +2008,10 @@ int run_block_main(apples_ctx *ctx, QueryBlock &qb, const Feeder *feed) {
             // the member distances of accepted clusters on the matrix cores (k_cluster_dist_mfma) unless APPLES_DBG_NO_CLUSTER_MFMA
             sa.cl_mfma = (!csd && !(ctx->dbg & APPLES_DBG_NO_CLUSTER_MFMA)) ? 1 : 0;
             sa.overlap = ctx->params.overlap_frac; sa.rep_stride = a.reps_pad; sa.tmp_d = w.dist;
-            if (!csd && !cl_long && a.cl_xoff) {  // panels with bytes beyond ACGT- held as gaps: the mask planes, and the rule's own table
+            if (!csd && a.cl_xoff) {  // panels with bytes beyond ACGT- held as gaps: the mask planes, and the rule's own table
                 sa.rep_x = a.rep_x; sa.rep_bad = a.rep_bad; sa.x_rm = a.x_rm; sa.cl_xoff = a.cl_xoff;
-                if (a.rep_x || ctx->jc_mmax_true) {  // (the representatives' survivors are a superset: k_cluster_rep_fix)
+                // (cl_long: k_long_exotic_fix, above, has put the representatives' survivors right already)
+                if (!cl_long && (a.rep_x || ctx->jc_mmax_true)) {  // (the representatives' survivors are a superset: k_cluster_rep_fix)
                     sa.ex_mmax = ctx->jc_mmax_true ? ctx->jc_mmax_true : ctx->jc_mmax;
                     sa.ex_all = ctx->jc_mmax_true ? 1 : 0;
                 }
@@ -2540,7 +2587,9 @@ int apples_set_params(apples_ctx *ctx, const apples_params *params) {
                                      : jc_bound_long_table(ctx->aln.L, params->overlap_frac, params->filt_threshold);
         // (reference rows with bytes beyond ACGT-, DevAlign::x_off: the pass counts them as gaps and k_long_exotic_fix tests every
         // survivor against the rule itself -- the table through jc_lut where the caller supplies one)
+        // (a clustered context's pass runs over the representatives alone: DevAlign::rep_xoff, loosened by THEIR most such bytes)
         if (ctx->aln.x_off && ctx->aln.ex_max > 0) bound = loosen_bound(bound, ctx->aln.L, ctx->aln.ex_max);
+        else if (ctx->aln.rep_xoff && ctx->aln.rep_ex_max > 0) bound = loosen_bound(bound, ctx->aln.L, ctx->aln.rep_ex_max);
         if (ctx->aln.ref_f4 || bound[0] < 0) {
             if (dev_upload(ctx, &ctx->jc_bound_long, bound.data(), (int64_t)bound.size())) return 1;
             HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -2593,6 +2642,7 @@ void apples_ctx_destroy(apples_ctx *ctx) {
     dev_free(a.raw); dev_free(a.d_slot_row); dev_free(a.packed); dev_free(a.ref_f4); dev_free(a.rep_f4); dev_free(a.rep_boff); dev_free(a.rep_loff); dev_free(a.loose_mp); dev_free(a.blk_rec_i); dev_free(a.blk_rec_e); dev_free(a.blk_rec_c); dev_free(a.blk_rec_p); dev_free(a.blk_pk_i); dev_free(a.blk_pk_e); dev_free(a.blk_stat[0]); dev_free(a.blk_stat[1]); dev_free(a.rep_soff); dev_free(a.cl_order); dev_free(a.mem_block); dev_free(a.blk_root); dev_free(a.blk_rslot); dev_free(a.blk_nodes); dev_free(a.e_of_slot); dev_free(a.e_of_blk); dev_free(a.e_node); dev_free(a.lvl_e); dev_free(a.rep_packed); dev_free(a.packed_rm); dev_free(a.aa_rep_idx); dev_free(a.aa_rep_mask); dev_free(a.aa_cm_idx); dev_free(a.aa_cm_mask); dev_free(a.aa_idx); dev_free(a.aa_mask); dev_free(a.sd_ref4); dev_free(a.sd_nvr); dev_free(a.aa_rows); dev_free(a.aa_mrows); dev_free(ctx->sd_tq4); dev_free(ctx->sd_list_img); dev_free(ctx->sd_list_ints); dev_free(a.slot_node); dev_free(a.slot_level); dev_free(a.lvl_slots);
     dev_free(a.slot_rep); dev_free(a.slot_mpos); dev_free(a.rep_slot); dev_free(a.rep_moff); dev_free(a.mem_slot);
     dev_free(a.rep_x); dev_free(a.rep_bad); dev_free(a.x_rm); dev_free(a.cl_xoff); dev_free(a.x_off); dev_free(a.x_rows);
+    dev_free(a.rep_xoff); dev_free(a.rep_xrows);
     dev_free(ctx->jc_lut); dev_free(ctx->jc_mmax); dev_free(ctx->jc_mmax_true); dev_free(ctx->jc_mmax_q); dev_free(ctx->jc_bound_long); dev_free(ctx->blosum); dev_free(ctx->d_col_perm); dev_free(ctx->d_col_node);
     dev_free(ctx->d_col_level);
     for (int i = 0; i < 8; ++i)
@@ -3175,7 +3225,7 @@ const char *apples_describe(apples_ctx *ctx) {
              "{\"device\": \"%s\", \"compute_units\": %d, \"n_nodes\": %d, \"height\": %d, \"max_children\": %d, \"n_rows\": %lld, "
              "\"n_refs\": %lld, \"n_reps\": %lld, \"length\": %d, \"code_planes\": %d, \"all_singleton\": %d, "
              "\"packed_bytes\": %lld, \"batch\": %lld, \"sweep_workgroups\": %d, \"sweep_team_cap\": %lld, \"sweep_big_workgroups\": %d, \"jc_lut\": %d, \"sweep\": \"%s\", "
-             "\"fused_distance_pass\": \"%s\", \"gemm_split_sites\": %d, \"k_split_launches\": %lld, \"k_split_exotic_fixes\": %lld, \"cluster_k_split_launches\": %lld, \"fp4_reference_image_bytes\": %lld, \"sweep_layout\": \"%s\", \"cluster_fused\": %d, "
+             "\"fused_distance_pass\": \"%s\", \"gemm_split_sites\": %d, \"k_split_launches\": %lld, \"k_split_exotic_fixes\": %lld, \"cluster_k_split_launches\": %lld, \"cluster_k_split_exotic_fixes\": %lld, \"fp4_reference_image_bytes\": %lld, \"sweep_layout\": \"%s\", \"cluster_fused\": %d, "
              "\"scoredist_filter\": %d, \"scoredist_image_bytes\": %lld, \"cluster_blocks\": %d, \"block_items_last_batch\": %d, \"block_tiles_last_batch\": %d, "
              "\"exotic_symbols_as_gaps\": %d, \"exotic_sites_max_per_row\": %d, \"eight_plane_copy\": %d, \"cluster_exotic_clusters\": %d, "
              "\"ragged_rows\": %d, \"row_small\": %lld, \"big_rows\": %lld, \"big_rows_last_batch\": %d, \"full_rows_for_good\": %d, "
@@ -3194,6 +3244,7 @@ const char *apples_describe(apples_ctx *ctx) {
              dist_gemm_long_usable(ctx) ? GEMM_SPLIT_STEPS * 64 : 0, (long long)ctx->gemm_long_launches,
              (long long)ctx->long_exotic_fixes,  // ... and of k_long_exotic_fix behind it (reference rows with bytes beyond ACGT-: DevAlign::x_off)
              (long long)ctx->cluster_long_launches,  // ... of the same kernel over the representatives' image (clustered contexts of 8 192+ sites)
+             (long long)ctx->cluster_long_fixes,  // ... and of k_long_exotic_fix behind those (representatives with bytes beyond ACGT-: DevAlign::rep_xoff)
              (long long)(a.ref_f4 ? a.slots_pad * (int64_t)a.G * 128 : 0),
              // how the level-loop sweep knows a query's subtree: merged level lists / node bits in LDS / tagged node map
              // (lean: sweep_lean.hip on big binary trees -- the workspace decides; before there is one, what a plain MLSE / ME pass will get)

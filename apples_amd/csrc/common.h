@@ -137,7 +137,8 @@ struct DevAlign {
     //     pass's survivors (a site where the row has such a byte and the query a letter is valid and a mismatch).
     bool ex_ok = false;           // the context takes this route (JC69, matrix-core passes enabled, L < 8192; singleton clusters, or a
                                   // clustered context on the fused route by representatives: rep_x / x_rm below in place of ex_off / ex_site;
-                                  // from 8 192 sites on: singleton contexts on the K-split route whose reference holds such a byte, x_off / x_rows)
+                                  // from 8 192 sites on: singleton contexts on the K-split route whose reference holds such a byte, x_off / x_rows,
+                                  // and clustered contexts on the long fused route, clean or not: rep_x / x_rm and rep_xoff / rep_xrows)
     uint4 *packed8 = nullptr;     // [G][9][slots_pad]; built with the first such byte, in the reference or in a query block
     int32_t *ex_off = nullptr;    // [n_rows + 1] CSR over slots, or nullptr: the reference rows hold no such byte
     uint16_t *ex_site = nullptr;  // [ex_off[n_rows]] sites, ascending per slot
@@ -159,7 +160,13 @@ struct DevAlign {
     uint4 *x_rm = nullptr;        // the members' of the flagged clusters: cl_xoff[c] + g * size(c) + position
     int32_t *cl_xoff = nullptr;   // [n_reps] first word of the cluster's masks in x_rm, -1: no member holds such a byte; nullptr: no cluster
     int32_t n_xclusters = 0;      // flagged clusters
-    uint8_t *rep_f4 = nullptr;    // alignments of GEMM_LONG_MIN_L sites and more: the representatives' rows in representative order as a compact fp4
+    // ... and from GEMM_LONG_MIN_L sites on (the long forms; ex_ok holds for such a context whether its reference is clean or not):
+    // the same panels' masks, and for the representatives' pass -- k_jc69_gemm_long's EX form over rep_f4, k_long_exotic_fix behind
+    // it -- the flagged representatives' planes once more representative-major, as x_off / x_rows are slot-major
+    int32_t *rep_xoff = nullptr;  // [reps_pad] index of the representative's plane in rep_xrows, -1: clean (or padding); nullptr: none flagged
+    uint4 *rep_xrows = nullptr;   // [flagged representatives][G]
+    int32_t rep_ex_max = 0;       // most such sites in one representative's row (what the pass's screen is loosened by)
+    uint8_t *rep_f4 = nullptr;   // alignments of GEMM_LONG_MIN_L sites and more: the representatives' rows in representative order as a compact fp4
                                   // operand image ([reps_pad][2G] blocks in ref_f4's tiled form; padding rows all-gap) -- k_jc69_gemm_long reads it
     // ... and of scoredist contexts (the default route of -p): the representatives' rows in representative order, in the layout
     // of aa_idx / aa_mask with reps_pad in place of slots_pad (what k_scoredist runs over in place of every slot)
@@ -380,6 +387,7 @@ struct apples_ctx {
     int64_t gemm_long_launches = 0;    // launches of k_jc69_gemm_long so far (describe(): "k_split_launches")
     int64_t long_exotic_fixes = 0;     // launches of k_long_exotic_fix behind it (describe(): "k_split_exotic_fixes")
     int64_t cluster_long_launches = 0; // ... over the representatives' image of a clustered context (describe(): "cluster_k_split_launches")
+    int64_t cluster_long_fixes = 0;    // ... and of k_long_exotic_fix behind those (DevAlign::rep_xoff; describe(): "cluster_k_split_exotic_fixes")
     double *blosum = nullptr;  // 21x21 table (row/col 20 = gap -> 0)
     uint8_t *sd_tq4 = nullptr; // [20][20] fp4 codes of the table rounded down to the grid {0, .5, 1, 1.5, 2, 3, 4, 6} / 4 (dist_sd.hip)
     Workspace ws;
@@ -450,7 +458,8 @@ int launch_pack_aa(apples_ctx *ctx, const uint8_t *d_raw, int64_t n_rows, int L,
                    int64_t slots_pad, bool query_layout, hipStream_t st = nullptr, const int32_t *d_src_row = nullptr);
 // the mask panels of a clustered context with bytes beyond ACGT- (DevAlign::rep_x / x_rm), from a.raw; d_rep_x may be nullptr
 int launch_pack_exotic_masks(apples_ctx *ctx, const int32_t *d_cl_xoff, uint4 *d_x_rm, uint4 *d_rep_x);
-// ... one plane per flagged slot (DevAlign::x_off / x_rows); d_x_cnt[x_off[slot]] += the slot's such sites (the caller zeroes it)
+// ... one plane per flagged slot (DevAlign::x_off / x_rows); d_x_cnt[x_off[slot]] += the slot's such sites (the caller zeroes it;
+// d_x_rows may be nullptr: the counts alone)
 int launch_pack_exotic_mask_rows(apples_ctx *ctx, const int32_t *d_x_off, uint4 *d_x_rows, int32_t *d_x_cnt);
 // the same for the n rows of a query block (d_raw: its rows back to back; d_idx: per query the index of its plane in d_planes, -1: clean)
 int launch_pack_query_masks(apples_ctx *ctx, const uint8_t *d_raw, int64_t n, const int32_t *d_idx, uint4 *d_planes, int32_t *d_cnt);

@@ -996,8 +996,9 @@ int launch_exotic_fix(apples_ctx *ctx, const QueryBlock &qb, int64_t q0, int64_t
 // compacted by ballot, in row order, to the start of the segment: k_jc69 MODE 1's format.  A lane reads its entry before any lane
 // of the wavefront writes, and no other wavefront touches the segment.
 // Padding rows and all-gap queries have k = 0 and valid = 0: the exact test drops them.
-// row_off: row of the pass -> index of its plane in `masks`, -1 for a clean row (today DevAlign::x_off over the slots; the
-// representatives' image of a clustered context would bring a map of its own).
+// row_off: row of the pass -> index of its plane in `masks`, -1 for a clean row: DevAlign::x_off / x_rows over the slots of a
+// singleton context, rep_xoff / rep_xrows over the representatives' image of a clustered one (stride = reps_pad; what leaves is
+// what k_select_clusters<..., LONG> reads: representative indices with their fp64 distances).
 namespace {
 __global__ __launch_bounds__(APPLES_TPB) void k_long_exotic_fix(int32_t *__restrict__ seg_slot, int32_t *__restrict__ seg_cnt,
                                                                double *__restrict__ seg_d, int64_t stride, const uint4 *__restrict__ qp,
@@ -1057,7 +1058,7 @@ int launch_long_exotic_fix(apples_ctx *ctx, const QueryBlock &qb, int64_t q0, in
     hipLaunchKernelGGL(k_long_exotic_fix, dim3((unsigned)nq), dim3(APPLES_TPB), 0, ctx->stream, seg_slot, seg_cnt, seg_d, rows,
                        qb.packed, q0, a.G, a.L, row_off, masks, ctx->params.overlap_frac, ctx->params.filt_threshold, ctx->jc_lut);
     HIP_TRY(ctx, hipGetLastError());
-    ++ctx->long_exotic_fixes;
+    ++(masks == a.rep_xrows ? ctx->cluster_long_fixes : ctx->long_exotic_fixes);  // (the representatives' pass of a clustered context)
     return 0;
 }
 

@@ -878,7 +878,8 @@ int launch_counts_gemm_long(apples_ctx *ctx, const QueryBlock &qb, int64_t q0, i
     }
     const int64_t grid = std::max(8, ctx->n_cu / 8 * 8);  // persistent: one workgroup per CU, a multiple of the 8 XCDs
     const int R = (a.G * 2 - 2) % 3;
-    const bool ex = !reps && a.x_off != nullptr;  // the reference image holds bytes beyond ACGT- as gaps: k_long_exotic_fix follows
+    // the image holds bytes beyond ACGT- as gaps: k_long_exotic_fix follows (the caller launches it: over x_off, or over rep_xoff)
+    const bool ex = reps ? a.rep_xoff != nullptr : a.x_off != nullptr;
 #define GL_LAUNCH(R_, T_, E_)                                                                                          \
     hipLaunchKernelGGL((k_jc69_gemm_long<R_, T_, E_>), dim3((unsigned)grid), dim3(GL_QT * 2), 0, ctx->stream, image, qb.qf4, q0, \
                        rows, a.G * 2, nq, a.L, TQ, TR, seg_slot, seg_cnt, seg_d, ctx->jc_bound_long,            \

@@ -249,7 +249,7 @@ __global__ __launch_bounds__(APPLES_TPB) void k_pack_exotic_mask_rows(const uint
     // (W4 is a multiple of 4: the four words of a group sit in four consecutive lanes of one wavefront)
     const uint4 px = make_uint4(x, __shfl_down(x, 1, 64), __shfl_down(x, 2, 64), __shfl_down(x, 3, 64));
     if (xo >= 0 && (w & 3) == 0) {
-        x_rows[(int64_t)xo * G + (w >> 2)] = px;
+        if (x_rows) x_rows[(int64_t)xo * G + (w >> 2)] = px;  // (nullptr: the counts alone -- a clustered context's members)
         const int n = __popc(px.x) + __popc(px.y) + __popc(px.z) + __popc(px.w);
         if (n) atomicAdd(x_cnt + xo, n);
     }

@@ -708,7 +708,8 @@ __device__ __forceinline__ void cluster_count(const uint4 &rm, const uint4 &r0, 
 //   the survivors come as representative indices with their fp64 distances in a.rep_seg_d (k_jc69 MODE 1's format) and not as
 //   packed 13-bit counts for a table; by_query keeps the query's first 64 word groups in sh_q as the short form does and takes the
 //   groups beyond from the query's packed tile in global memory -- every lane reads the same address, a broadcast out of L1 / L2 --
-//   and ends in jc69_from_counts (libm's log, or the caller's table where there still is one: 8 192 sites).
+//   and ends in jc69_from_counts (libm's log, or the caller's table where there still is one: 8 192 sites).  A row with bytes beyond
+//   ACGT- (xmem / xrep) adds k = popc(its mask word & the query's gap plane) per group to both counts first, as the short form does.
 template <int PHASE, int CAP = SELECT_CLUSTERS_ACC_CAP, bool LISTED = (PHASE == 4), int TPB = APPLES_TPB, bool SHORT_ONLY = false, bool LONG = false>
 __global__ __launch_bounds__(TPB) void k_select_clusters(SelectArgs a) {
     constexpr int ACC_CAP = CAP, NW = TPB / WAVE;
@@ -820,7 +821,7 @@ __global__ __launch_bounds__(TPB) void k_select_clusters(SelectArgs a) {
     // cluster-major panel with the cluster's size as stride (the lanes holding consecutive members read consecutive 16
     // bytes), or the representative panel with its padded length
     // (xrow: the row's mask plane of bytes beyond ACGT-, word g at xrow[g * sz], or nullptr -- such a site under a letter of the
-    // query is one more valid site and one more mismatch; short forms only)
+    // query is one more valid site and one more mismatch)
     auto by_query = [&](const uint4 *row, int64_t sz, const uint4 *xrow) -> double {
         uint32_t nv = 0, nmis = 0;
         int g = 0;
@@ -850,6 +851,14 @@ __global__ __launch_bounds__(TPB) void k_select_clusters(SelectArgs a) {
                 const uint4 *u = qw + (int64_t)g * 48;
                 cluster_count(row[(int64_t)(g * 3) * sz], row[(int64_t)(g * 3 + 1) * sz], row[(int64_t)(g * 3 + 2) * sz], u[0], u[1], u[2], nv, nmis);
             }
+            if (xrow) {  // the row's mask word per group against the query's gap plane: sh_q, then the packed tile as above
+                uint32_t k = 0;
+                for (g = 0; g < G; ++g) {
+                    const uint4 x = xrow[(int64_t)g * sz], m = g < Gs ? sh_q[g * 3] : qw[(int64_t)g * 48];
+                    k += __popc(x.x & m.x) + __popc(x.y & m.y) + __popc(x.z & m.z) + __popc(x.w & m.w);
+                }
+                nv += k; nmis += k;
+            }
             return jc69_from_counts(nmis, nv, a.L, a.overlap, a.seg_lut);
         }
         for (; g + CLUSTER_UNROLL <= G; g += CLUSTER_UNROLL) {  // 3 x CLUSTER_UNROLL loads in flight before the first is used
@@ -874,8 +883,8 @@ __global__ __launch_bounds__(TPB) void k_select_clusters(SelectArgs a) {
         return a.seg_lut[(int64_t)nv * (nv + 1) / 2 + nmis];
     };
     // a member's mask plane: cluster c, position mp (nullptr: the cluster is clean) / a representative's
-    auto xmem = [&](int c, int mp) -> const uint4 * { return (!LONG && a.cl_xoff && a.cl_xoff[c] >= 0) ? a.x_rm + a.cl_xoff[c] + mp : nullptr; };
-    auto xrep = [&](int64_t j) -> const uint4 * { return (!LONG && a.rep_x && a.rep_bad[j]) ? a.rep_x + j : nullptr; };
+    auto xmem = [&](int c, int mp) -> const uint4 * { return (a.cl_xoff && a.cl_xoff[c] >= 0) ? a.x_rm + a.cl_xoff[c] + mp : nullptr; };
+    auto xrep = [&](int64_t j) -> const uint4 * { return (a.rep_x && a.rep_bad[j]) ? a.rep_x + j : nullptr; };
     // ---- accepted representatives: the survivors of the representative pass, in representative order
     const int64_t n_seg = a.rep_stride >> 6;
     const int32_t *cnt = a.seg_cnt + q * n_seg;
@@ -1431,7 +1440,8 @@ __global__ __launch_bounds__(CL_TILES_TPB) void k_cluster_tiles(SelectArgs a) {
 // addresses: broadcasts), and the thread adds the pair counts of its up to 16 queries.  Same counts and same table lookup as
 // phase 0 of k_select_clusters, so the same bits.  Persistent workgroups walk the tile table.
 // LONG (alignments of GEMM_LONG_MIN_L to 65 535 sites): the same loops -- 32-bit counts hold any such length -- and every pair's
-// distance from jc69_from_counts in place of the table look-up (the table where the caller still supplies one)
+// distance from jc69_from_counts in place of the table look-up (the table where the caller still supplies one); the k term of a
+// flagged cluster (cl_xoff) goes into both counts before it, as before the look-up
 #define CL_GC 4
 template <bool LONG>
 __global__ __launch_bounds__(APPLES_TPB) void k_cluster_dist(SelectArgs a) {
@@ -1459,7 +1469,7 @@ __global__ __launch_bounds__(APPLES_TPB) void k_cluster_dist(SelectArgs a) {
             const uint4 *row = a.packed_rm + (int64_t)mb * (G * 3) + mc0 + ml;
             // a cluster with bytes beyond ACGT- among its members (workgroup-uniform): one more word per group, the member's mask
             // plane of such sites -- under a letter of the query each is one more valid site and one more mismatch
-            const int xo = (!LONG && a.cl_xoff) ? a.cl_xoff[c] : -1;
+            const int xo = a.cl_xoff ? a.cl_xoff[c] : -1;
             const uint4 *xrow = xo >= 0 ? a.x_rm + xo + mc0 + ml : nullptr;
             for (int g0 = 0; g0 < G; g0 += CL_GC) {
                 __syncthreads();  // the list above is written / the previous chunk's words are read
@@ -1543,19 +1553,22 @@ __global__ __launch_bounds__(APPLES_TPB) void k_cluster_dist(SelectArgs a) {
 // wavefronts per SIMD (80 bytes of scratch per lane at CLM_WAVES = 2, where the short form has 28): the long form is compiled for ONE
 // wavefront per SIMD and uses no scratch ("Clustered route, long forms", has the resource report; the alternative, a second kernel over
 // parked counts, was not built).
-// EX (short form, clusters with bytes beyond ACGT- among their members: SelectArgs::cl_xoff): the panel holds those bytes as gaps; a
+// EX (clusters with bytes beyond ACGT- among their members: SelectArgs::cl_xoff): the panel holds those bytes as gaps; a
 // third image, Xm, is expanded from the members' mask plane of such sites (x_rm; fp4 1.0 where the bit is set, same piece-major form,
 // one component) and a fifth MFMA per 32 x 32 block and 64-site block multiplies it with the queries' validity fragment, which is in
 // registers anyway, into a third accumulator set: k = the member's such sites under a letter of the query, each one more valid site
 // and one more mismatch (integers, exact in f32).  The look-up is lut[(valid + k)(valid + k + 1) / 2 + mism + k].  Two launches
 // share the tile table: EX = false is the code as it was and passes over the flagged clusters' tiles, EX = true takes only those
 // (wavefront-uniform per tile).  192 accumulators: compiled for CLM_EX_WAVES wavefronts per SIMD.
+// LONG and EX together (flagged clusters of a context of GEMM_LONG_MIN_L sites and more): the third accumulator set on top of the
+// long form's fp64 epilogue, fused -- jc69_from_counts(mism + k, valid + k, ...) per pair.  One wavefront per SIMD has 512 registers
+// a lane: 256 VGPRs + 246 AGPRs, no scratch ("Clustered route, long forms with mask planes"), so the counts are
+// not parked for a second kernel.
 #ifndef CLM_EX_WAVES
 #define CLM_EX_WAVES 1
 #endif
 template <bool LONG, bool EX = false>
 __global__ __launch_bounds__(WAVE, LONG ? 1 : (EX ? CLM_EX_WAVES : CLM_WAVES)) void k_cluster_dist_mfma(SelectArgs a) {
-    static_assert(!(LONG && EX), "the mask planes exist on the short route only");
     // the images of one 64-site block, piece-major: piece (component c, quarter k) of row r -- 8 bytes, 16 sites -- at [c * 4 + k][r].  A lane
     // expands its own row (it holds the row's plane words), so a store instruction writes 64 consecutive pieces and a fragment read
     // 32 consecutive ones: no bank conflicts either way (row-major images as in k_jc69_mfma cost this kernel four-way conflicts on
@@ -1585,7 +1598,7 @@ __global__ __launch_bounds__(WAVE, LONG ? 1 : (EX ? CLM_EX_WAVES : CLM_WAVES)) v
         const int4 tile = a.cl_tiles[t];
         const int c = tile.x, nqt = tile.z;
         const int mb = a.rep_moff[c], sz = a.rep_moff[c + 1] - mb;
-        if (!LONG && a.cl_xoff && (a.cl_xoff[c] >= 0) != EX) continue;  // (the other launch's tile)
+        if (a.cl_xoff && (a.cl_xoff[c] >= 0) != EX) continue;  // (the other launch's tile)
         __builtin_amdgcn_wave_barrier();  // (the previous tile's readers of sh_q / sh_o)
         {
             const int2 it = a.cl_items[tile.y + (lane < nqt ? lane : 0)];
@@ -1915,12 +1928,11 @@ static int launch_select_clusters_t(apples_ctx *ctx, const SelectArgs &a, int64_
     if (sd) hipLaunchKernelGGL(k_cluster_dist_sd<4>, dim3((unsigned)(ctx->n_cu * std::max(per_cu, 1))), dim3(APPLES_TPB), 0, ctx->stream, a);
     else if (a.cl_mfma) {
         hipLaunchKernelGGL(k_cluster_dist_mfma<LONG>, dim3((unsigned)(ctx->n_cu * 4 * (LONG ? 1 : CLM_WAVES))), dim3(WAVE), 0, ctx->stream, a);  // (18 KB of LDS per wavefront: eight per CU)
-        if constexpr (!LONG)  // the tiles of the clusters with bytes beyond ACGT- (the launch above passed over them)
-            if (a.cl_xoff) {
-                HIP_TRY(ctx, hipGetLastError());
-                hipLaunchKernelGGL((k_cluster_dist_mfma<false, true>), dim3((unsigned)(ctx->n_cu * 4 * CLM_EX_WAVES)), dim3(WAVE), 0, ctx->stream, a);
-                HIP_TRY(ctx, hipGetLastError());
-            }
+        if (a.cl_xoff) {  // the tiles of the clusters with bytes beyond ACGT- (the launch above passed over them)
+            HIP_TRY(ctx, hipGetLastError());
+            hipLaunchKernelGGL((k_cluster_dist_mfma<LONG, true>), dim3((unsigned)(ctx->n_cu * 4 * (LONG ? 1 : CLM_EX_WAVES))), dim3(WAVE), 0, ctx->stream, a);
+            HIP_TRY(ctx, hipGetLastError());
+        }
     }
     else hipLaunchKernelGGL(k_cluster_dist<LONG>, dim3((unsigned)(ctx->n_cu * std::max(per_cu, 1))), dim3(APPLES_TPB), 0, ctx->stream, a);
     // the second form's last phase beside the first's, on the spare stream: a hundred-odd workgroups of 1 024 threads (their
