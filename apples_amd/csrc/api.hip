@@ -746,6 +746,8 @@ int setup_alignment(apples_ctx *ctx, const apples_tree *t, const apples_alignmen
                 if (dev_upload(ctx, &a.ex_off, off.data(), (int64_t)off.size())) return 1;
                 if (dev_upload(ctx, &a.ex_site, sites.data(), (int64_t)sites.size())) return 1;
             } else {
+                // (the representatives' most: what the screen of a query block with such bytes is loosened by, query_screen)
+                for (int64_t j = 0; j < a.n_reps; ++j) a.rep_ex_max = std::max(a.rep_ex_max, off[rep_slot[j] + 1] - off[rep_slot[j]]);
                 cl_bad.swap(bad);  // (the mask planes come with the panels, below; ex_max is what set_params loosens the table by)
             }
             if (ensure_packed8(ctx)) return 1;
@@ -1334,6 +1336,7 @@ int make_block(apples_ctx *ctx, const uint8_t *queries, int64_t n, const int32_t
 // profiles/query_exotic_c3.txt), D = 1 is 4 % ahead, D = 4 behind, D = 64 six times slower.  A clean reference has D = 0 whatever
 // the queries hold: no query is kept off the route there (6.6 x ahead of the 8-plane pass).
 constexpr int64_t QUERY_EXOTIC_CAP = 1;
+constexpr int64_t CLUSTER_QUERY_EXOTIC_REP_MAX = 16;  // (the clustered route's bound, exotic_queries; the largest measured value at which it is ahead)
 
 // The screen of the launches over a block whose queries hold up to `top` bytes beyond ACGT- as gaps in their fp4 image
 // (apples_ctx::jc_mmax_q; the arithmetic: dist.hip, k_query_exotic_fix).  A pair's true counts are (v + t, m + t - j): t <= T =
@@ -1343,12 +1346,13 @@ constexpr int64_t QUERY_EXOTIC_CAP = 1;
 // (-1 where no t qualifies).  The window matters at the table's lower end only, where the overlap rule -V keeps the smaller count
 // out; "+ D" is the whole loosening elsewhere, and D = 0 for a clean reference.  Built once and rebuilt when a block asks for
 // more: a looser screen is still a superset, k_query_exotic_fix tests every survivor against the rule itself.
-int query_screen(apples_ctx *ctx, int64_t top) {
-    const int64_t L = ctx->aln.L, D = std::min<int64_t>(ctx->aln.ex_max, top);
+// (ex_max: the most such bytes in a row the launches run over -- the reference rows', or the representatives' on the clustered route)
+int query_screen(apples_ctx *ctx, int64_t top, int64_t ex_max) {
+    const int64_t L = ctx->aln.L, D = std::min<int64_t>(ex_max, top);
     if (ctx->h_mmax.empty()) { ctx->err = "query_screen: no integer form of the threshold rule"; return 1; }
     if (ctx->jc_mmax_q && ctx->mmax_q_top >= top && ctx->mmax_q_D >= D) return 0;
     const std::vector<int32_t> &rule = ctx->h_mmax;
-    const int64_t T = std::min<int64_t>(L, (int64_t)ctx->aln.ex_max + top);
+    const int64_t T = std::min<int64_t>(L, ex_max + top);
     std::vector<int32_t> scr((size_t)L + 1, -1);
     for (int64_t v = 0; v <= L; ++v) {
         int64_t best = INT64_MIN;
@@ -1373,7 +1377,9 @@ int query_screen(apples_ctx *ctx, int64_t top) {
 //     the matrix-core pass -- its fp4 image holds such bytes as gaps --, gets one mask plane per flagged query (QueryBlock::qx), its
 //     launches a loosened screen (query_screen) and k_query_exotic_fix behind them.  A query that would loosen the screen by more
 //     than QUERY_EXOTIC_CAP does not take the route: those go to the ex_block by the few-rule above;
-//   * else (too many of those as well, a clustered context, the K-split route): the whole block through the 8-plane kernels
+//   * more, in a clustered context of that length on the fused route by representatives: the same with the representatives' pass
+//     screened, select.hip: k_cluster_rep_query_fix behind it and the QX forms of the member-distance kernels; no cap by default;
+//   * else (too many of those as well, the long clustered route, the K-split route): the whole block through the 8-plane kernels
 //     (exact8: no matrix-core pass for it).
 // `queries` / `self_row`: the caller's.
 int exotic_queries(apples_ctx *ctx, QueryBlock *qb, const uint8_t *queries, const int32_t *self_row) {
@@ -1393,7 +1399,15 @@ int exotic_queries(apples_ctx *ctx, QueryBlock *qb, const uint8_t *queries, cons
     if (idx.empty()) return 0;
     const int64_t few = std::min<int64_t>(std::max<int64_t>(16, qb->n / 20), 2048);
     if ((int64_t)idx.size() > few) {
-        const bool in_scope = a.all_singleton && ctx->params.model == APPLES_JC69 && a.planes == 2 && a.L < 8192 && qb->qf4 &&
+        // (clustered: the fused selection by representatives with its panels built -- run_block_main's cfused; APPLES_NO_CLUSTER_QUERY_EXOTIC
+        // keeps such blocks on the 8-plane kernels as before)
+        // ... while no representative holds more than CLUSTER_QUERY_EXOTIC_REP_MAX such bytes (knob APPLES_CLUSTER_QUERY_EXOTIC_REP_MAX):
+        // the context's own table is loosened by that number for every block, and at 200 the fused pass of even a clean block costs
+        // more than the 8-plane pass of a flagged one (59 against 50 ms, profiles/clustered_query_exotic.txt; at 16 it is 3.3 - 30 against 46 - 49)
+        const bool clustered = !a.all_singleton && a.rep_packed && a.packed_rm && ctx->jc_lut && !(ctx->dbg & APPLES_DBG_NO_FUSE) &&
+                               !knob_on(ctx, "APPLES_NO_CLUSTER_QUERY_EXOTIC") &&
+                               a.rep_ex_max <= knob(ctx, "APPLES_CLUSTER_QUERY_EXOTIC_REP_MAX", CLUSTER_QUERY_EXOTIC_REP_MAX);
+        const bool in_scope = (a.all_singleton || clustered) && ctx->params.model == APPLES_JC69 && a.planes == 2 && a.L < 8192 && qb->qf4 &&
                               ctx->jc_mmax && !ctx->h_mmax.empty() && !knob_on(ctx, "APPLES_NO_MMAX");
         if (!in_scope) { qb->exact8 = true; return 0; }
         // the flagged queries' mask planes and how many such bytes each holds
@@ -1410,11 +1424,14 @@ int exotic_queries(apples_ctx *ctx, QueryBlock *qb, const uint8_t *queries, cons
                   hipStreamSynchronize(ctx->stream) != hipSuccess;  // (the vectors are locals)
         dev_free(d_cnt);
         if (bad) { if (ctx->err.empty()) ctx->err = "mask planes of the queries with bytes beyond ACGT-: failed"; return 1; }
-        const int64_t cap = knob(ctx, "APPLES_QUERY_EXOTIC_CAP", QUERY_EXOTIC_CAP);
+        // (the clustered route has no cap of its own: its only screened pass runs over the representatives, and a loosened screen lets at
+        // most all of them through -- the knob still applies where it is set)
+        const int64_t cap = knob(ctx, "APPLES_QUERY_EXOTIC_CAP", clustered ? INT64_MAX : QUERY_EXOTIC_CAP);
+        const int64_t row_max = clustered ? a.rep_ex_max : a.ex_max;
         std::vector<int32_t> over;
         int32_t top = 0;
         for (size_t k = 0; k < idx.size(); ++k) {
-            if (std::min<int64_t>(cnt[k], a.ex_max) > cap) over.push_back(idx[k]);
+            if (std::min<int64_t>(cnt[k], row_max) > cap) over.push_back(idx[k]);
             else top = std::max(top, cnt[k]);
         }
         if ((int64_t)over.size() > few || over.size() == idx.size()) {  // (nobody left for the route: as before)
@@ -1788,7 +1805,12 @@ int run_block_main(apples_ctx *ctx, QueryBlock &qb, const Feeder *feed) {
     // a block whose queries hold bytes beyond ACGT- as gaps in its fp4 image (exotic_queries): its launches test through the
     // loosened screen, k_query_exotic_fix follows each
     const bool qfix = fused && a.all_singleton && qb.qx != nullptr && fused_counts_format(ctx, qb);
-    if (qfix && query_screen(ctx, qb.qx_top)) return 1;
+    if (qfix && query_screen(ctx, qb.qx_top, a.ex_max)) return 1;
+    // ... and of a clustered context on the fused route by representatives: the representatives' pass tests through the screen
+    // loosened by their such bytes, select.hip: k_cluster_rep_query_fix follows it, the member distances take the kernels' QX forms
+    const bool cqx = cfused && !csd && !cl_long && !a.all_singleton && qb.qx != nullptr;
+    if (qb.qx && !a.all_singleton && !cqx) { ctx->err = "a query block with mask planes outside the clustered fused route"; return 1; }
+    if (cqx && query_screen(ctx, qb.qx_top, a.rep_ex_max)) return 1;
     // the overlapped route applies (comment above; APPLES_EXOTIC_FIX_KERNEL, a diagnostic, puts a kernel that writes the batch's
     // n_obs behind the GEMM: serial -- and so does k_query_exotic_fix)
     const long long ovl_knob = knob(ctx, "APPLES_OVERLAP", -1);
@@ -1990,7 +2012,7 @@ int run_block_main(apples_ctx *ctx, QueryBlock &qb, const Feeder *feed) {
                     launch_long_exotic_fix(ctx, qb, q0, nq, ctx->sd_rep_d, w.seg_slot, w.seg_cnt, a.rep_xoff, a.rep_xrows, a.reps_pad)) return 1;
             } else {
                 HIP_TRY(ctx, hipMemsetAsync(w.seg_cnt, 0, (size_t)nq * (a.reps_pad / 64) * sizeof(int32_t), front));
-                if (launch_counts_reps(ctx, qb, q0, nq, w.seg_slot, w.seg_cnt)) return 1;
+                if (launch_counts_reps(ctx, qb, q0, nq, w.seg_slot, w.seg_cnt, cqx ? ctx->jc_mmax_q : nullptr)) return 1;
             }
             HIP_TRY(ctx, hipEventRecord(e[1], front));
             ++launches;
@@ -2015,6 +2037,17 @@ int run_block_main(apples_ctx *ctx, QueryBlock &qb, const Feeder *feed) {
                     sa.ex_mmax = ctx->jc_mmax_true ? ctx->jc_mmax_true : ctx->jc_mmax;
                     sa.ex_all = ctx->jc_mmax_true ? 1 : 0;
                 }
+            }
+            if (cqx) {  // queries with such bytes: every survivor of the loosened pass gets its exact counts and the rule's own table
+                sa.qx_idx = qb.qx_idx + q0; sa.qx = qb.qx; sa.qpacked8 = qb.packed8 + q0 * a.G * 9; sa.packed8 = a.packed8; sa.slots8 = a.slots_pad;
+                sa.rep_panel = a.rep_packed;
+                sa.ex_mmax = ctx->jc_mmax_true ? ctx->jc_mmax_true : ctx->jc_mmax;
+                sa.ex_all = 1;
+                ++ctx->cluster_query_exotic_fixes;
+                ctx->cluster_query_exotic_D = std::min<int64_t>(a.rep_ex_max, qb.qx_top);  // (this block's; the cached table may be looser)
+                // (measured, DESIGN.md section 5: the matrix-core QX form is ahead on tiles of clean clusters, the bit-count form on tiles
+                // of flagged ones, where the former runs its second pass; the knobs send every such tile one way, for the comparison)
+                sa.qx_mfma = knob_on(ctx, "APPLES_CLUSTER_QX_BITCOUNT") ? 0 : (knob_on(ctx, "APPLES_CLUSTER_QX_MFMA") ? 2 : 1);
             }
             sa.slow_hint = w.slow_list + w.batch;
             sa.lvl_slots = a.lvl_slots;
@@ -3229,7 +3262,8 @@ const char *apples_describe(apples_ctx *ctx) {
              "\"scoredist_filter\": %d, \"scoredist_image_bytes\": %lld, \"cluster_blocks\": %d, \"block_items_last_batch\": %d, \"block_tiles_last_batch\": %d, "
              "\"exotic_symbols_as_gaps\": %d, \"exotic_sites_max_per_row\": %d, \"eight_plane_copy\": %d, \"cluster_exotic_clusters\": %d, "
              "\"ragged_rows\": %d, \"row_small\": %lld, \"big_rows\": %lld, \"big_rows_last_batch\": %d, \"full_rows_for_good\": %d, "
-             "\"overlap\": %d, \"overlap_batches\": %d, \"query_exotic_fixes\": %lld, \"query_exotic_loosened_by\": %lld}",
+             "\"overlap\": %d, \"overlap_batches\": %d, \"query_exotic_fixes\": %lld, \"query_exotic_loosened_by\": %lld, "
+             "\"cluster_query_exotic_fixes\": %lld, \"cluster_query_exotic_loosened_by\": %lld}",
              name, cus, ctx->tree.n_nodes, ctx->tree.height, ctx->tree.max_children, (long long)a.n_rows, (long long)a.n_refs,
              (long long)a.n_reps, a.L, a.planes, a.all_singleton ? 1 : 0,
              (long long)((int64_t)a.G * (a.planes + 1) * a.slots_pad * 16), (long long)ctx->ws.batch, ctx->ws.small.wgs,
@@ -3266,7 +3300,9 @@ const char *apples_describe(apples_ctx *ctx) {
              // the last block's pass: distance GEMM of batch b + 1 beside selection and sweep of batch b (run_block_main); its device batches
              ctx->overlap, ctx->overlap_batches,
              // launches of k_query_exotic_fix (query blocks with bytes beyond ACGT- on the matrix-core pass: exotic_queries), the D of the last
-             (long long)ctx->query_exotic_fixes, (long long)ctx->query_exotic_D);
+             (long long)ctx->query_exotic_fixes, (long long)ctx->query_exotic_D,
+             // ... of k_cluster_rep_query_fix (the same on the clustered route by representatives), the D of the last
+             (long long)ctx->cluster_query_exotic_fixes, (long long)ctx->cluster_query_exotic_D);
     ctx->desc = buf;
     return ctx->desc.c_str();
 }

@@ -243,7 +243,8 @@ struct QueryBlock {
     int32_t *ex_idx = nullptr;       // ... and which queries they are [ex_block->n] (run_block places them last and copies the structs over)
     // ... or, many of them in a singleton context of fewer than 8 192 sites: the block STAYS on the matrix-core pass (its fp4 image
     // holds such bytes as gaps), the pass's screen is loosened for its launches and dist.hip: k_query_exotic_fix gives every survivor
-    // its exact counts (api.hip: exotic_queries)
+    // its exact counts (api.hip: exotic_queries).  A clustered context of that length on the fused route by representatives: the same,
+    // with select.hip: k_cluster_rep_query_fix behind the representatives' pass and the QX forms of the member-distance kernels
     uint4 *qx = nullptr;          // [flagged queries][G] mask planes, bit = the site holds such a byte (the gap plane's bit order); non-null: this route
     int32_t *qx_idx = nullptr;    // [n_pad] index of the query's plane in qx, -1: a clean query
     int32_t qx_top = 0;           // most such bytes in one query that takes the route (the screen is loosened by it: apples_ctx::jc_mmax_q)
@@ -379,6 +380,8 @@ struct apples_ctx {
     int64_t mmax_q_top = -1, mmax_q_D = -1;  // what jc_mmax_q was built for: such bytes per query at most, D (-1: not built)
     int64_t query_exotic_fixes = 0;    // launches of k_query_exotic_fix (describe(): "query_exotic_fixes")
     int64_t query_exotic_D = 0;        // D of the last such launch (describe(): "query_exotic_loosened_by")
+    int64_t cluster_query_exotic_fixes = 0;  // launches of k_cluster_rep_query_fix (describe(): "cluster_query_exotic_fixes")
+    int64_t cluster_query_exotic_D = 0;      // D of the last such launch (describe(): "cluster_query_exotic_loosened_by")
     int32_t *jc_bound_long = nullptr;  // [65 536] (the kernel indexes with a 16-bit count; -1 beyond L) the K-split pass's integer screen, a
                                        // superset of the rule.  Without a distance table: -1 where the overlap rule excludes the valid
                                        // count, else min(valid, m* + 1), m* = the largest mismatch count the host's log lets pass
@@ -563,6 +566,13 @@ struct SelectArgs {
     // flagged cluster counts k, and the representatives' survivors are counted and tested again before phase 1 reads them
     // (k_cluster_rep_fix, with ex_mmax / ex_all above)
     const uint4 *rep_x, *x_rm; const int32_t *rep_bad, *cl_xoff;
+    // ... and in the QUERIES of a block that stays on this route (QueryBlock::qx; all nullptr for any other block): per query the index
+    // of its mask plane in qx (-1: clean), the batch's queries and the reference rows in their 8-plane forms (the raw bytes: which of
+    // the sites that hold such a byte in both rows differ), the latter with rows of slots8 words.  k_cluster_rep_query_fix takes
+    // k_cluster_rep_fix's place, the QX forms of the member-distance kernels the plain ones'
+    const int32_t *qx_idx; const uint4 *qx, *qpacked8, *packed8; int64_t slots8;
+    int qx_mfma;                        // ... the tiles that hold a flagged query on the matrix cores (k_cluster_dist_mfma's QX = 2 form), not by bit counts
+                                        // (k_cluster_dist_qx): 0 none, 1 those of clean clusters (the default: DESIGN.md section 5), 2 all
     int cl_mfma;                        // the member distances of accepted clusters on the matrix cores (k_cluster_dist_mfma), not by bit counts (k_cluster_dist)
     double *tmp_d;            // [nq][stride] member distances before the ordered emission
     int flat_pref;            // k_select_fast: the segment counts' prefix fits LDS (set by the launcher)
@@ -618,7 +628,9 @@ int launch_select_clusters_listed(apples_ctx *ctx, const SelectArgs &a, int64_t 
 #define SELECT_CLUSTERS_HUGE_CAP 16384 // ... and on the third, for references of more than BIG_CAP clusters: the offsets in LDS (64 KB), the other lists in global scratch
 #define SELECT_CLUSTERS_BIG_LIST 1024 // queries a batch may send to that form (more: the general route)
 #define SELECT_CLUSTERS_MAX_SLOTS 524288  // k_select_clusters' bitmap: 256 threads x runs of 32 words (80 KB of LDS at that size; 229 376 until round 6)
-int launch_counts_reps(apples_ctx *ctx, const QueryBlock &qb, int64_t q0, int64_t nq, int32_t *seg_slot, int32_t *seg_cnt);
+// (screen: as launch_counts_gemm's, below)
+int launch_counts_reps(apples_ctx *ctx, const QueryBlock &qb, int64_t q0, int64_t nq, int32_t *seg_slot, int32_t *seg_cnt,
+                       const int32_t *screen = nullptr);
 int launch_build_cluster_panels(apples_ctx *ctx);  // listed queries, needs segmin_d/segmin_i; baseobs <= 256
 int launch_permute_cols(apples_ctx *ctx, const double *in, double *out, const int32_t *perm, int64_t nq, int64_t n_cols);
 bool dist_mfma_enabled(const apples_ctx *ctx);

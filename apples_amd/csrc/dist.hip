@@ -595,13 +595,15 @@ int launch_build_cluster_panels(apples_ctx *ctx) {
 
 // the fused matrix-core pass over the representatives alone: survivors (0 <= d <= threshold) per 64-representative
 // segment, in the packed (position, valid, mism) format, rows of reps_pad entries
-int launch_counts_reps(apples_ctx *ctx, const QueryBlock &qb, int64_t q0, int64_t nq, int32_t *seg_slot, int32_t *seg_cnt) {
+int launch_counts_reps(apples_ctx *ctx, const QueryBlock &qb, int64_t q0, int64_t nq, int32_t *seg_slot, int32_t *seg_cnt,
+                       const int32_t *screen) {
     if (nq == 0) return 0;
     const DevAlign &a = ctx->aln;
     dim3 grid((unsigned)(a.reps_pad / 128), (unsigned)((nq + MF_QT - 1) / MF_QT));
     hipLaunchKernelGGL((k_jc69_mfma<1>), grid, dim3(MF_TPB), 0, ctx->stream, a.rep_packed,
                        qb.qf4 + q0 * (int64_t)a.G * 256, (double *)nullptr, (uint32_t *)nullptr, a.n_reps, a.reps_pad, a.G, nq,
-                       a.L, ctx->params.overlap_frac, ctx->jc_lut, ctx->params.filt_threshold, seg_slot, seg_cnt, ctx->jc_mmax);
+                       a.L, ctx->params.overlap_frac, ctx->jc_lut, ctx->params.filt_threshold, seg_slot, seg_cnt,
+                       screen ? screen : ctx->jc_mmax);
     HIP_TRY(ctx, hipGetLastError());
     return 0;
 }

@@ -696,6 +696,29 @@ __device__ __forceinline__ void cluster_count(const uint4 &rm, const uint4 &r0, 
             __popc(((q0.z ^ r0.z) | (q1.z ^ r1.z)) & m2_) + __popc(((q0.w ^ r0.w) | (q1.w ^ r1.w)) & m3_);
 }
 
+// QX: what a QUERY with bytes beyond ACGT- (its plane of them: xq; the panels and its own packed words hold them as gaps) adds to the
+// pair counts of one word group -- DESIGN.md section 3: k1 = popc(Xq & Mr), such a byte over a letter of the row, valid and a
+// mismatch; k3 = popc(Xq & Xr), such bytes in both, valid, and k3x of them differ: the OR over the eight planes of the raw bytes of
+// (Pq ^ Pr) under Xq & Xr, read only where that word is not empty (q8: the query's eight plane words of the group, back to back; r8:
+// the row's, r8_stride words apart).  The row's own term, k2 = popc(Mq & Xr), is the callers' as it was.
+__device__ __forceinline__ void cluster_count_qx(const uint4 &xq, const uint4 &rm, const uint4 &rx, const uint4 *__restrict__ q8,
+                                                 const uint4 *__restrict__ r8, int64_t r8_stride, uint32_t &nv, uint32_t &nmis) {
+    const uint32_t k1 = __popc(xq.x & rm.x) + __popc(xq.y & rm.y) + __popc(xq.z & rm.z) + __popc(xq.w & rm.w);
+    const uint4 b = make_uint4(xq.x & rx.x, xq.y & rx.y, xq.z & rx.z, xq.w & rx.w);
+    uint32_t k3 = 0, k3x = 0;
+    if (b.x | b.y | b.z | b.w) {
+        uint4 df = make_uint4(0, 0, 0, 0);
+#pragma unroll
+        for (int p = 0; p < 8; ++p) {
+            const uint4 u = q8[p], v = r8[(int64_t)p * r8_stride];
+            df.x |= u.x ^ v.x; df.y |= u.y ^ v.y; df.z |= u.z ^ v.z; df.w |= u.w ^ v.w;
+        }
+        k3 = __popc(b.x) + __popc(b.y) + __popc(b.z) + __popc(b.w);
+        k3x = __popc(df.x & b.x) + __popc(df.y & b.y) + __popc(df.z & b.z) + __popc(df.w & b.w);
+    }
+    nv += k1 + k3; nmis += k1 + k3x;
+}
+
 //   CAP = accepted clusters a workgroup's lists hold: ACC_CAP for the launch over all queries; the queries beyond it (1 % at C3
 //   size: observed sets of tens of thousands) are listed by phase 1 and go through the same phases once more with CAP = BIG_CAP,
 //   a workgroup per list entry (LISTED; 60 KB of lists, so one workgroup per CU: a launch of their own keeps that occupancy
@@ -710,8 +733,14 @@ __device__ __forceinline__ void cluster_count(const uint4 &rm, const uint4 &r0, 
 //   groups beyond from the query's packed tile in global memory -- every lane reads the same address, a broadcast out of L1 / L2 --
 //   and ends in jc69_from_counts (libm's log, or the caller's table where there still is one: 8 192 sites).  A row with bytes beyond
 //   ACGT- (xmem / xrep) adds k = popc(its mask word & the query's gap plane) per group to both counts first, as the short form does.
-template <int PHASE, int CAP = SELECT_CLUSTERS_ACC_CAP, bool LISTED = (PHASE == 4), int TPB = APPLES_TPB, bool SHORT_ONLY = false, bool LONG = false>
+//   QX (phases 0 and 4, which form member distances themselves, of a block whose QUERIES hold bytes beyond ACGT-: SelectArgs::qx_idx):
+//   by_query adds cluster_count_qx's terms for a flagged query -- its plane and its eight raw planes come from global memory, every
+//   lane the same address; the row's raw planes from the reference's 8-plane form through the row's slot.  A clean query of such a
+//   block pays one look at qx_idx.
+template <int PHASE, int CAP = SELECT_CLUSTERS_ACC_CAP, bool LISTED = (PHASE == 4), int TPB = APPLES_TPB, bool SHORT_ONLY = false, bool LONG = false,
+          bool QX = false>
 __global__ __launch_bounds__(TPB) void k_select_clusters(SelectArgs a) {
+    static_assert(!QX || (!LONG && (PHASE == 0 || PHASE == 4)), "the QX form: phases 0 and 4 of the short route");
     constexpr int ACC_CAP = CAP, NW = TPB / WAVE;
     extern __shared__ unsigned long long dyn_bits[];  // [n_words] member bits in slot order, then uint16 [n_words]: the set bits before the
                                                       // word inside its thread's run of 16 words (sh_base: before the run)
@@ -822,7 +851,9 @@ __global__ __launch_bounds__(TPB) void k_select_clusters(SelectArgs a) {
     // bytes), or the representative panel with its padded length
     // (xrow: the row's mask plane of bytes beyond ACGT-, word g at xrow[g * sz], or nullptr -- such a site under a letter of the
     // query is one more valid site and one more mismatch)
-    auto by_query = [&](const uint4 *row, int64_t sz, const uint4 *xrow) -> double {
+    // (slot8, QX: the row's slot in the reference's 8-plane form)
+    const int qxi = QX ? a.qx_idx[q] : -1;
+    auto by_query = [&](const uint4 *row, int64_t sz, const uint4 *xrow, int64_t slot8) -> double {
         uint32_t nv = 0, nmis = 0;
         int g = 0;
         if (LONG) {
@@ -880,6 +911,12 @@ __global__ __launch_bounds__(TPB) void k_select_clusters(SelectArgs a) {
             }
             nv += k; nmis += k;
         }
+        if (QX && qxi >= 0) {
+            const uint4 *q8 = a.qpacked8 + ((q >> 4) * G * 16 + (q & 15)) * 9 + 1;  // group g's eight planes at (g * 16) * 9 beyond this
+            for (g = 0; g < G; ++g)
+                cluster_count_qx(a.qx[(int64_t)qxi * G + g], row[(int64_t)(g * 3) * sz], xrow ? xrow[(int64_t)g * sz] : make_uint4(0, 0, 0, 0),
+                                 q8 + (int64_t)g * 144, a.packed8 + ((int64_t)g * 9 + 1) * a.slots8 + slot8, a.slots8, nv, nmis);
+        }
         return a.seg_lut[(int64_t)nv * (nv + 1) / 2 + nmis];
     };
     // a member's mask plane: cluster c, position mp (nullptr: the cluster is clean) / a representative's
@@ -898,7 +935,7 @@ __global__ __launch_bounds__(TPB) void k_select_clusters(SelectArgs a) {
         for (int64_t j0 = 0; j0 < a.n_reps; j0 += TPB) {
             const int64_t j = j0 + tid;
             // (scoredist: the full rows of the representative pass hold them)
-            const double d = j < a.n_reps ? (sd ? a.rep_dist[q * a.rep_stride + j] : by_query(a.rep_panel + j, a.rep_stride, xrep(j))) : -1.0;
+            const double d = j < a.n_reps ? (sd ? a.rep_dist[q * a.rep_stride + j] : by_query(a.rep_panel + j, a.rep_stride, xrep(j), QX ? a.rep_slot[j] : 0)) : -1.0;
             if (j < a.n_reps) reprow[j] = d;
             const int in = j < a.n_reps && d >= 0 && d <= a.thr;
             int tot;
@@ -1132,7 +1169,8 @@ __global__ __launch_bounds__(TPB) void k_select_clusters(SelectArgs a) {
                 if (sh_off[mid] <= m) lo = mid; else hi = mid;
             }
             const double d = sd ? sd_dist(a.mem_slot[sh_mb[lo] + (m - sh_off[lo])])
-                                : by_query(a.packed_rm + (int64_t)sh_mb[lo] * (G * 3) + (m - sh_off[lo]), sh_off[lo + 1] - sh_off[lo], xmem(sh_rep[lo], m - sh_off[lo]));
+                                : by_query(a.packed_rm + (int64_t)sh_mb[lo] * (G * 3) + (m - sh_off[lo]), sh_off[lo + 1] - sh_off[lo], xmem(sh_rep[lo], m - sh_off[lo]),
+                                           QX ? a.mem_slot[sh_mb[lo] + (m - sh_off[lo])] : 0);
             tmp[m] = d;
             c += !(d < 0);
         }
@@ -1156,7 +1194,7 @@ __global__ __launch_bounds__(TPB) void k_select_clusters(SelectArgs a) {
             if (tid == 0) { sh_rep[n_acc_all] = bi; sh_mb[n_acc_all] = mb0; sh_off[n_acc_all + 1] = M + sz; }
             c = 0;
             for (int mp = tid; mp < sz; mp += TPB) {
-                const double d = sd ? sd_dist(a.mem_slot[mb0 + mp]) : by_query(a.packed_rm + (int64_t)mb0 * (G * 3) + mp, sz, xmem(bi, mp));
+                const double d = sd ? sd_dist(a.mem_slot[mb0 + mp]) : by_query(a.packed_rm + (int64_t)mb0 * (G * 3) + mp, sz, xmem(bi, mp), QX ? a.mem_slot[mb0 + mp] : 0);
                 tmp[M + mp] = d;
                 c += !(d < 0);
             }
@@ -1197,7 +1235,7 @@ __global__ __launch_bounds__(TPB) void k_select_clusters(SelectArgs a) {
                 if (mbk_[e] >= 0) { d_[e] = 1.0; continue; }
                 slot_[e] = a.mem_slot[mb + mp];  // (on its way with the member's distance / words below: neither waits for the other)
                 if (PHASE >= 3) d_[e] = tmp[m];  // k_cluster_dist (phase 4: the block above) left it there
-                else d_[e] = by_query(a.packed_rm + (int64_t)mb * (G * 3) + mp, sh_off[lo + 1] - sh_off[lo], xmem(sh_rep[lo], mp));
+                else d_[e] = by_query(a.packed_rm + (int64_t)mb * (G * 3) + mp, sh_off[lo + 1] - sh_off[lo], xmem(sh_rep[lo], mp), QX ? a.mem_slot[mb + mp] : 0);
             }
         }
 #pragma unroll
@@ -1533,6 +1571,123 @@ __global__ __launch_bounds__(APPLES_TPB) void k_cluster_dist(SelectArgs a) {
     }
 }
 
+// k_cluster_dist_qx (a block whose QUERIES hold such bytes, SelectArgs::qx_idx; the short route): k_cluster_dist once more; the flagged queries' planes of such bytes are
+// staged beside their packed words (zero for a clean query), and a pair whose query word holds one adds cluster_count_qx's terms:
+// k1 from the member's letter plane in registers, k3 / k3x against the member's mask word and -- only where both hold such a byte
+// in the group -- the raw planes of both from the 8-plane forms.  A clean query of the tile costs one test of a staged word per group.
+// Beside k_cluster_dist_mfma (a.cl_mfma) this form serves the tiles that hold a flagged query and passes over the others, which are
+// that kernel's; without it, every tile.
+__global__ __launch_bounds__(APPLES_TPB) void k_cluster_dist_qx(SelectArgs a) {
+    __shared__ uint4 sh_qw[64][CL_GC * 3];
+    __shared__ uint4 sh_xw[64][CL_GC];
+    __shared__ int sh_q[64], sh_o[64], sh_xi[64];
+    const int tid = threadIdx.x;
+    const int G = a.G;
+    const int n_tiles = *a.cl_ntiles;
+    for (int t = blockIdx.x; t < n_tiles; t += gridDim.x) {
+        const int4 tile = a.cl_tiles[t];
+        const int c = tile.x, nqt = tile.z;
+        const int mb = a.rep_moff[c], sz = a.rep_moff[c + 1] - mb;
+        __syncthreads();  // the previous tile's last readers of sh_q / sh_o / sh_qw
+        int my_xi = -1;
+        if (tid < nqt) {
+            const int2 it = a.cl_items[tile.y + tid];
+            sh_q[tid] = it.x; sh_o[tid] = it.y;
+            sh_xi[tid] = my_xi = a.qx_idx[it.x];
+        }
+        if (!__syncthreads_or(my_xi >= 0) && a.cl_mfma) continue;  // (no flagged query in the tile: the matrix-core launch's)
+        // (... and so is a tile with one where SelectArgs::qx_mfma says so: 2 every such tile, 1 those of clean clusters)
+        if (a.cl_mfma && (a.qx_mfma == 2 || (a.qx_mfma == 1 && !(a.cl_xoff && a.cl_xoff[c] >= 0)))) continue;
+        for (int mc0 = 0; mc0 < sz; mc0 += APPLES_TPB) {  // (clusters beyond 256 members: in chunks)
+            const int P = sz - mc0 < APPLES_TPB ? sz - mc0 : APPLES_TPB, QL = APPLES_TPB / P;
+            const int ml = tid % P, jl = tid / P;
+            const bool active = jl < QL;
+            // (beside the matrix-core form the tiles hold up to 64 queries, a pass of this loop serves 16 QL of them: jb walks the tile)
+            auto pass = [&](const int jb) {
+            uint32_t nv[16], nmis[16];
+#pragma unroll
+            for (int k = 0; k < 16; ++k) { nv[k] = 0; nmis[k] = 0; }
+            const uint4 *row = a.packed_rm + (int64_t)mb * (G * 3) + mc0 + ml;
+            // a cluster with bytes beyond ACGT- among its members (workgroup-uniform): one more word per group, the member's mask
+            // plane of such sites -- under a letter of the query each is one more valid site and one more mismatch
+            const int xo = a.cl_xoff ? a.cl_xoff[c] : -1;
+            const uint4 *xrow = xo >= 0 ? a.x_rm + xo + mc0 + ml : nullptr;
+            const int64_t slot8 = active ? a.mem_slot[mb + mc0 + ml] : 0;  // (the member's row in the reference's 8-plane form)
+            for (int g0 = 0; g0 < G; g0 += CL_GC) {
+                __syncthreads();  // the list above is written / the previous chunk's words are read
+                for (int i = tid; i < nqt * (CL_GC * 3); i += APPLES_TPB) {
+                    const int j = i / (CL_GC * 3), w = i % (CL_GC * 3), g = g0 + w / 3, pl = w % 3;
+                    const int64_t q = sh_q[j];
+                    sh_qw[j][w] = g < G ? a.qpacked[(((q >> 4) * G + g) * 16 + (q & 15)) * 3 + pl] : make_uint4(0, 0, 0, 0);
+                }
+                for (int i = tid; i < nqt * CL_GC; i += APPLES_TPB) {
+                        const int j = i / CL_GC, g = g0 + i % CL_GC, xi = sh_xi[j];
+                        sh_xw[j][i % CL_GC] = (xi >= 0 && g < G) ? a.qx[(int64_t)xi * G + g] : make_uint4(0, 0, 0, 0);
+                    }
+                uint4 mw[CL_GC * 3];
+                if (active) {
+#pragma unroll
+                    for (int w = 0; w < CL_GC * 3; ++w)
+                        mw[w] = g0 + w / 3 < G ? row[(int64_t)((g0 + w / 3) * 3 + w % 3) * sz] : make_uint4(0, 0, 0, 0);
+                }
+                uint4 xw[CL_GC];
+#pragma unroll
+                for (int gg = 0; gg < CL_GC; ++gg) xw[gg] = make_uint4(0, 0, 0, 0);
+                if (active && xo >= 0) {
+#pragma unroll
+                    for (int gg = 0; gg < CL_GC; ++gg) xw[gg] = g0 + gg < G ? xrow[(int64_t)(g0 + gg) * sz] : make_uint4(0, 0, 0, 0);
+                }
+                __syncthreads();
+                if (active) {
+#pragma unroll
+                    for (int k = 0; k < 16; ++k) {
+                        const int j = jb + jl + k * QL;
+                        if (j < nqt) {
+#pragma unroll
+                            for (int gg = 0; gg < CL_GC; ++gg)
+                                cluster_count(mw[gg * 3], mw[gg * 3 + 1], mw[gg * 3 + 2], sh_qw[j][gg * 3], sh_qw[j][gg * 3 + 1],
+                                              sh_qw[j][gg * 3 + 2], nv[k], nmis[k]);
+                            if (xo >= 0) {
+                                uint32_t kx = 0;
+#pragma unroll
+                                for (int gg = 0; gg < CL_GC; ++gg) {
+                                    const uint4 qm = sh_qw[j][gg * 3];
+                                    kx += __popc(xw[gg].x & qm.x) + __popc(xw[gg].y & qm.y) + __popc(xw[gg].z & qm.z) + __popc(xw[gg].w & qm.w);
+                                }
+                                nv[k] += kx; nmis[k] += kx;
+                            }
+                            {
+                                const int64_t q = sh_q[j];
+#pragma unroll
+                                for (int gg = 0; gg < CL_GC; ++gg) {
+                                    const uint4 xq = sh_xw[j][gg];  // (all zero: a clean query, or beyond the last group)
+                                    if (xq.x | xq.y | xq.z | xq.w)
+                                        cluster_count_qx(xq, mw[gg * 3], xw[gg], a.qpacked8 + (((q >> 4) * G + g0 + gg) * 16 + (q & 15)) * 9 + 1,
+                                                         a.packed8 + ((int64_t)(g0 + gg) * 9 + 1) * a.slots8 + slot8, a.slots8, nv[k], nmis[k]);
+                                }
+                            }
+                        }
+                    }
+                }
+            }
+            if (active) {
+#pragma unroll
+                for (int k = 0; k < 16; ++k) {
+                    const int j = jb + jl + k * QL;
+                    if (j < nqt) {
+                        const double d = a.seg_lut[(int64_t)nv[k] * (nv[k] + 1) / 2 + nmis[k]];
+                        a.tmp_d[row_start(a.row_off, sh_q[j], a.stride) + sh_o[j] + mc0 + ml] = d;
+                        // clade blocks: a member the reference drops, an exact match or the query's own row -- the item goes without
+                        if (a.item_bad && (!(d > 0) || (a.self_slot && a.mem_slot[mb + mc0 + ml] == a.self_slot[sh_q[j]]))) a.item_bad[tile.y + j] = 1;
+                    }
+                }
+            }
+            };
+            for (int jb = 0; jb < nqt; jb += 16 * QL) pass(jb);
+        }
+    }
+}
+
 // The same on the matrix cores (the default): a wavefront = a tile of up to 64 queries x 64 of the cluster's members at a time, the
 // pair counts as in k_jc69_mfma (dist.hip: acc1 = sum t.t over three components, acc2 = valid; mism = (3 valid - acc1) / 4, exact
 // in the f32 accumulators) -- four v_mfma_f32_32x32x64_f8f6f4 per 32 x 32 block of pairs and 64-site block where k_cluster_dist
@@ -1567,8 +1722,23 @@ __global__ __launch_bounds__(APPLES_TPB) void k_cluster_dist(SelectArgs a) {
 #ifndef CLM_EX_WAVES
 #define CLM_EX_WAVES 1
 #endif
-template <bool LONG, bool EX = false>
+// QX (a block whose QUERIES hold such bytes, SelectArgs::qx_idx).  QX = 1: the same code, which passes over the tiles that hold a
+// flagged query; a tile of clean queries is what it was.  QX = 2 (with EX's third accumulator set) takes exactly those tiles, of
+// flagged and of clean clusters alike: the third set's operands become (M|X)q . (M|X)r -- a fourth image, Xq, is expanded from the
+// queries' letter word OR their word of such bytes, the members' from letter word OR mask word -- so that s3 = valid exactly and
+// K = s3 - s2 = k1 + k2 + k3 in the one extra MFMA per block the EX form has.  mism = m + K holds for every pair but those with
+// k3 > k3x (the same such byte in both rows at a site): the epilogue parks (valid, m + K) of the 64 x 64 pairs in LDS, and a second
+// pass, rolled, walks the tile's flagged queries (wavefront-uniform: their words are scalar loads) with the lanes along the members
+// that hold such bytes: k3 - k3x by bit counts (the raw planes of both 8-plane forms where Xq & Xr is not empty), the look-up and
+// the store once more where that is not zero.  (The member distances are used BY VALUE -- every valid one is an observation of the
+// least-squares fit -- so the pass cannot stop at the pairs near the threshold.)
+template <bool LONG, bool EX = false, int QX = 0>
 __global__ __launch_bounds__(WAVE, LONG ? 1 : (EX ? CLM_EX_WAVES : CLM_WAVES)) void k_cluster_dist_mfma(SelectArgs a) {
+    static_assert(QX != 2 || (EX && !LONG), "QX = 2: the third accumulator set, the short route");
+    constexpr bool QF = QX == 2;
+    __shared__ uint2 Xq[QF ? 4 : 1][64];         // QF: the queries' letters and such bytes together (validity nibbles)
+    __shared__ uint32_t sh_cnt[QF ? 64 : 1][64]; // QF: (valid << 16 | m + K) per (query, member) for the second pass
+    __shared__ int sh_xi[QF ? 64 : 1], sh_xany[QF ? 64 : 1];
     // the images of one 64-site block, piece-major: piece (component c, quarter k) of row r -- 8 bytes, 16 sites -- at [c * 4 + k][r].  A lane
     // expands its own row (it holds the row's plane words), so a store instruction writes 64 consecutive pieces and a fragment read
     // 32 consecutive ones: no bank conflicts either way (row-major images as in k_jc69_mfma cost this kernel four-way conflicts on
@@ -1598,23 +1768,32 @@ __global__ __launch_bounds__(WAVE, LONG ? 1 : (EX ? CLM_EX_WAVES : CLM_WAVES)) v
         const int4 tile = a.cl_tiles[t];
         const int c = tile.x, nqt = tile.z;
         const int mb = a.rep_moff[c], sz = a.rep_moff[c + 1] - mb;
-        if (a.cl_xoff && (a.cl_xoff[c] >= 0) != EX) continue;  // (the other launch's tile)
+        if (!QF && a.cl_xoff && (a.cl_xoff[c] >= 0) != EX) continue;  // (the other launch's tile)
         __builtin_amdgcn_wave_barrier();  // (the previous tile's readers of sh_q / sh_o)
         {
             const int2 it = a.cl_items[tile.y + (lane < nqt ? lane : 0)];
             sh_q[lane] = it.x; sh_o[lane] = it.y;
             sh_self[lane] = a.self_slot ? a.self_slot[it.x] : -2;  // (-2: no member's slot; my_slot is -1 without the check)
+            if (QX) {
+                const int xi = lane < nqt ? a.qx_idx[it.x] : -1;
+                if ((__ballot(xi >= 0) != 0) != QF) continue;  // (wavefront-uniform: a tile with a flagged query is the QX = 2 launch's)
+                if (QF && a.qx_mfma == 1 && a.cl_xoff && a.cl_xoff[c] >= 0) continue;  // (... of a flagged cluster: k_cluster_dist_qx's by default)
+                if (QF) sh_xi[lane] = xi;
+            }
         }
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
         const int64_t myq = sh_q[lane];
         const uint4 *qsrc = a.qpacked + ((myq >> 4) * G * 16 + (myq & 15)) * 3;  // group g, plane pl at ((g * 16) * 3 + pl) beyond this
+        const uint4 *qxsrc = (QF && sh_xi[lane] >= 0) ? a.qx + (int64_t)sh_xi[lane] * G : nullptr;  // the lane's query: its words of such bytes
+        const int xo = QF ? (a.cl_xoff ? a.cl_xoff[c] : -1) : 0;
         const bool qi1 = nqt > 32;
         for (int mc0 = 0; mc0 < sz; mc0 += 64) {
             const int msz = sz - mc0 < 64 ? sz - mc0 : 64;
             const bool mj1 = msz > 32;
             const int ml = lane < msz ? lane : msz - 1;  // (lanes beyond the chunk repeat its last member: computed, not written)
             const uint4 *rsrc = a.packed_rm + (int64_t)mb * (G * 3) + mc0 + ml;
-            const uint4 *xsrc = EX ? a.x_rm + a.cl_xoff[c] + mc0 + ml : nullptr;  // group g at g * sz beyond this
+            const uint4 *xsrc = QF ? (xo >= 0 ? a.x_rm + xo + mc0 + ml : nullptr) : (EX ? a.x_rm + a.cl_xoff[c] + mc0 + ml : nullptr);  // group g at g * sz beyond this
+            uint32_t xacc = 0;  // QF: the lane's member holds such a byte at all
             v16f_t s1[2][2], s2[2][2], s3[EX ? 2 : 1][EX ? 2 : 1];
 #pragma unroll
             for (int i = 0; i < 2; ++i)
@@ -1622,13 +1801,18 @@ __global__ __launch_bounds__(WAVE, LONG ? 1 : (EX ? CLM_EX_WAVES : CLM_WAVES)) v
                 for (int j = 0; j < 2; ++j)
 #pragma unroll
                     for (int x = 0; x < 16; ++x) { s1[i][j][x] = 0.f; s2[i][j][x] = 0.f; if (EX) s3[i][j][x] = 0.f; }
-            uint4 qm, q0, q1, pm, p0, p1, px;
+            uint4 qm, q0, q1, pm, p0, p1, px, qxw;
             auto fetch = [&](int g, uint4 &am, uint4 &a0, uint4 &a1, uint4 &bm, uint4 &b0, uint4 &b1) {
                 const uint4 *qp = qsrc + (int64_t)g * 48;
                 am = qp[0]; a0 = qp[1]; a1 = qp[2];
                 const uint4 *rp = rsrc + (int64_t)(g * 3) * sz;
                 bm = rp[0]; b0 = rp[sz]; b1 = rp[2 * (int64_t)sz];
-                if (EX) px = xsrc[(int64_t)g * sz];
+                if (EX && !QF) px = xsrc[(int64_t)g * sz];
+                if (QF) {
+                    px = xsrc ? xsrc[(int64_t)g * sz] : make_uint4(0, 0, 0, 0);
+                    qxw = qxsrc ? qxsrc[g] : make_uint4(0, 0, 0, 0);
+                    xacc |= px.x | px.y | px.z | px.w;
+                }
             };
             fetch(0, qm, q0, q1, pm, p0, p1);
             for (int g = 0; g < G; ++g) {
@@ -1642,20 +1826,30 @@ __global__ __launch_bounds__(WAVE, LONG ? 1 : (EX ? CLM_EX_WAVES : CLM_WAVES)) v
                     if (EX) {
 #pragma unroll
                         for (int h = 0; h < 2; ++h) {  // (expand_row's validity nibbles alone, of the mask word)
-                            const uint32_t xw = y ? (h ? px.w : px.z) : (h ? px.y : px.x);
+                            uint32_t xw = y ? (h ? px.w : px.z) : (h ? px.y : px.x);
+                            if (QF) xw |= y ? (h ? pm.w : pm.z) : (h ? pm.y : pm.x);  // (M | X of the member)
 #pragma unroll
                             for (int k = 0; k < 2; ++k) Xm[2 * h + k][lane] = make_uint2(((xw >> (2 * k)) << 1) & 0x22222222u, (xw >> (2 * k)) & 0x22222222u);
+                            if (QF) {
+                                const uint32_t qw = (y ? (h ? qxw.w : qxw.z) : (h ? qxw.y : qxw.x)) | (y ? (h ? qm.w : qm.z) : (h ? qm.y : qm.x));
+#pragma unroll
+                                for (int k = 0; k < 2; ++k) Xq[2 * h + k][lane] = make_uint2(((qw >> (2 * k)) << 1) & 0x22222222u, (qw >> (2 * k)) & 0x22222222u);
+                            }
                         }
                     }
                     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
                     {
                         v4i_t fa[2][2], fb[2][2];  // [t1 | t2][row block]
-                        v4i_t fx[2];
+                        v4i_t fx[2], fxq[2];
                         if (EX) {
 #pragma unroll
                             for (int j = 0; j < 2; ++j) {
                                 const uint2 x0 = Xm[2 * fh][j * 32 + fr], x1 = Xm[2 * fh + 1][j * 32 + fr];
                                 fx[j] = v4i_t{(int)x0.x, (int)x0.y, (int)x1.x, (int)x1.y};
+                                if (QF) {
+                                    const uint2 y0 = Xq[2 * fh][j * 32 + fr], y1 = Xq[2 * fh + 1][j * 32 + fr];
+                                    fxq[j] = v4i_t{(int)y0.x, (int)y0.y, (int)y1.x, (int)y1.y};
+                                }
                             }
                         }
 #pragma unroll
@@ -1692,7 +1886,7 @@ __global__ __launch_bounds__(WAVE, LONG ? 1 : (EX ? CLM_EX_WAVES : CLM_WAVES)) v
                                     if ((i == 1 && !qi1) || (j == 1 && !mj1)) continue;  // (wave-uniform)
                                     if (cc < 3) s1[i][j] = mfma_f4(fa[set][i], fb[set][j], s1[i][j]);
                                     else s2[i][j] = mfma_f4(fa[set][i], fb[set][j], s2[i][j]);
-                                    if (EX && cc == 3) s3[i][j] = mfma_f4(fa[0][i], fx[j], s3[i][j]);  // (fa[0]: the queries' validity by now)
+                                    if (EX && cc == 3) s3[i][j] = mfma_f4(QF ? fxq[i] : fa[0][i], fx[j], s3[i][j]);  // (fa[0]: the queries' validity by now)
                                 }
                         }
                     }
@@ -1717,8 +1911,9 @@ __global__ __launch_bounds__(WAVE, LONG ? 1 : (EX ? CLM_EX_WAVES : CLM_WAVES)) v
                     double d[16];
 #pragma unroll
                     for (int x = 0; x < 16; ++x) {
-                        const int nv2 = (int)s2[i][j][x], kx = EX ? (int)s3[i][j][x] : 0;
+                        const int nv2 = (int)s2[i][j][x], kx = EX ? (int)s3[i][j][x] - (QF ? nv2 : 0) : 0;  // (QF: s3 = valid, K = s3 - s2)
                         const int nv = nv2 + kx, nmis = ((3 * nv2 - (int)s1[i][j][x]) >> 2) + kx;
+                        if (QF) sh_cnt[i * 32 + (x & 3) + 8 * (x >> 2) + 4 * fh][m] = ((uint32_t)nv << 16) | (uint32_t)nmis;
 #ifdef CL_EXP_NO_EPILOGUE  // (timing experiment: the main loop alone)
                         d[x] = (double)(nv + nmis);
 #elif defined(CL_EXP_NO_LOG)  // (timing experiment, long form: the epilogue's stores without its logarithms -- positive finite values, wrong placements)
@@ -1742,6 +1937,35 @@ __global__ __launch_bounds__(WAVE, LONG ? 1 : (EX ? CLM_EX_WAVES : CLM_WAVES)) v
                         }
                     }
                 }
+            if (QF && xo >= 0) {  // the second pass: k3 - k3x of the pairs (flagged query, member with such bytes)
+                sh_xany[lane] = (int)xacc;
+                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+                const bool mine = lane < msz && xacc != 0;
+                const int64_t slot8 = a.mem_slot[mb + mc0 + ml];
+                if (__ballot(mine) != 0)
+                    for (int jq = 0; jq < nqt; ++jq) {
+                        const int xi = __builtin_amdgcn_readfirstlane(sh_xi[jq]);
+                        if (xi < 0) continue;
+                        const int64_t q = __builtin_amdgcn_readfirstlane(sh_q[jq]);
+                        int corr = 0;
+                        if (mine)
+                            for (int g = 0; g < G; ++g) {
+                                const uint4 xq = a.qx[(int64_t)xi * G + g], xr = xsrc[(int64_t)g * sz];
+                                uint32_t v = 0, mm = 0;  // (k3, k3x through cluster_count_qx with an empty letter word)
+                                cluster_count_qx(xq, make_uint4(0, 0, 0, 0), xr, a.qpacked8 + (((q >> 4) * G + g) * 16 + (q & 15)) * 9 + 1,
+                                                 a.packed8 + ((int64_t)g * 9 + 1) * a.slots8 + slot8, a.slots8, v, mm);
+                                corr += (int)(v - mm);
+                            }
+                        if (corr > 0) {
+                            const uint32_t pk = sh_cnt[jq][lane];
+                            const int nv = (int)(pk >> 16), nmis = (int)(pk & 0xffffu) - corr;
+                            const double d = a.seg_lut[(int64_t)nv * (nv + 1) / 2 + nmis];
+                            a.tmp_d[row_start(a.row_off, q, a.stride) + sh_o[jq] + mc0 + lane] = d;
+                            if (a.item_bad && !(d > 0)) a.item_bad[tile.y + jq] = 1;
+                        }
+                    }
+                __builtin_amdgcn_wave_barrier();
+            }
         }
     }
 }
@@ -1871,18 +2095,89 @@ __global__ __launch_bounds__(APPLES_TPB) void k_cluster_rep_fix(SelectArgs a, in
     }
 }
 
+// The same behind a pass over a block whose QUERIES hold bytes beyond ACGT- as gaps in their fp4 image (SelectArgs::qx_idx; api.hip:
+// exotic_queries): the pass tested through the screen loosened for such blocks (apples_ctx::jc_mmax_q), so every survivor gets its
+// true counts -- valid = v + k1 + k2 + k3, mism = m + k1 + k2 + k3x (cluster_count_qx; k2 = k_cluster_rep_fix's term) -- and the
+// rule's own table.  One workgroup per query.  Dynamic LDS holds the query's letter plane, its plane of such bytes and, for a flagged
+// query, the eight planes of its raw bytes: G x (1 + 1 + 8) words of 16 bytes, 10 KB at 8 191 sites.  The wavefronts deal the
+// query's segments among themselves; a wavefront reads a segment's survivors in one load, then takes 64 / GL of them at a time, GL
+// = G rounded up to a power of two: lane (survivor, word group) reads the representative's letter word and mask word of its group
+// (rep_panel / rep_x) and, only where both rows hold such a byte in the group, the representative's raw planes from the
+// reference's 8-plane form through rep_slot; a butterfly over the GL lanes sums the two increments.  The survivors that pass are
+// rewritten in the order they came in (a ballot over the group leaders ranks them), the segment's count follows: the format phase 1
+// and the drep look-up of phase 3 read.  A clean query of the block takes the same path with k1 = k3 = 0; padding representatives,
+// which the loosened screen may let through, are dropped.
+__global__ __launch_bounds__(APPLES_TPB) void k_cluster_rep_query_fix(SelectArgs a, int32_t *__restrict__ seg_slot, int32_t *__restrict__ seg_cnt) {
+    extern __shared__ uint4 dyn_qx[];  // [G] letter plane, [G] plane of such bytes, [G][8] raw planes
+    const int64_t q = blockIdx.x;
+    const int G = a.G, tid = threadIdx.x;
+    uint4 *const sh_m = dyn_qx, *const sh_x = dyn_qx + G, *const sh_p = dyn_qx + 2 * G;
+    const int xi = a.qx_idx[q];
+    for (int g = tid; g < G; g += APPLES_TPB) {
+        sh_m[g] = a.qpacked[(((q >> 4) * G + g) * 16 + (q & 15)) * 3];
+        sh_x[g] = xi >= 0 ? a.qx[(int64_t)xi * G + g] : make_uint4(0, 0, 0, 0);
+    }
+    if (xi >= 0)
+        for (int i = tid; i < G * 8; i += APPLES_TPB)
+            sh_p[i] = a.qpacked8[(((q >> 4) * G + (i >> 3)) * 16 + (q & 15)) * 9 + 1 + (i & 7)];
+    __syncthreads();
+    int GL = 1;
+    while (GL < G) GL <<= 1;  // (G <= 64)
+    const int lane = tid & (WAVE - 1), g = lane & (GL - 1), sub = lane / GL, S = WAVE / GL;
+    const int64_t n_seg = a.rep_stride >> 6;
+    for (int64_t s = tid / WAVE; s < n_seg; s += APPLES_TPB / WAVE) {
+        const int c = min(seg_cnt[q * n_seg + s], 64);  // (wavefront-uniform)
+        if (c <= 0) continue;
+        int32_t *w = seg_slot + q * a.rep_stride + s * 64;
+        const int mine = lane < c ? w[lane] : 0;  // (the whole segment before anything of it is rewritten)
+        int out = 0;
+        for (int i0 = 0; i0 < c; i0 += S) {
+            const int i = i0 + sub;
+            const uint32_t pk = (uint32_t)__shfl(mine, i < c ? i : 0, WAVE);
+            const int64_t j = s * 64 + (pk >> 26);
+            const bool live = i < c && j < a.n_reps;
+            uint32_t dv = 0, dm = 0;
+            if (live && g < G) {
+                const uint4 rm = a.rep_panel[(int64_t)(g * 3) * a.rep_stride + j];
+                const uint4 rx = (a.rep_x && a.rep_bad[j]) ? a.rep_x[(int64_t)g * a.rep_stride + j] : make_uint4(0, 0, 0, 0);
+                const uint4 m = sh_m[g];
+                dv = dm = __popc(rx.x & m.x) + __popc(rx.y & m.y) + __popc(rx.z & m.z) + __popc(rx.w & m.w);
+                if (xi >= 0)
+                    cluster_count_qx(sh_x[g], rm, rx, sh_p + g * 8, a.packed8 + ((int64_t)g * 9 + 1) * a.slots8 + a.rep_slot[j], a.slots8, dv, dm);
+            }
+            for (int o = GL >> 1; o > 0; o >>= 1) { dv += __shfl_xor(dv, o, WAVE); dm += __shfl_xor(dm, o, WAVE); }
+            const int valid = (int)((pk >> 13) & 0x1fffu) + (int)dv, mism = (int)(pk & 0x1fffu) + (int)dm;
+            const bool pass = live && g == 0 && valid <= a.L && mism <= a.ex_mmax[valid];
+            const unsigned long long bal = __ballot(pass);
+            if (pass) w[out + __popcll(bal & ((1ull << lane) - 1ull))] = (int32_t)((pk & 0xfc000000u) | ((uint32_t)valid << 13) | (uint32_t)mism);
+            out += __popcll(bal);
+        }
+        if (lane == 0 && out != c) seg_cnt[q * n_seg + s] = out;
+    }
+}
+
 // (LONG: SelectArgs::cl_long -- the same launches with the kernels' long forms)
-template <bool LONG, int PHASE, int CAP = SELECT_CLUSTERS_ACC_CAP, bool LISTED = (PHASE == 4), int TPB = APPLES_TPB, bool SHORT_ONLY = false>
-static constexpr auto ksc() { return &k_select_clusters<PHASE, CAP, LISTED, TPB, SHORT_ONLY, LONG>; }
+template <bool LONG, int PHASE, int CAP = SELECT_CLUSTERS_ACC_CAP, bool LISTED = (PHASE == 4), int TPB = APPLES_TPB, bool SHORT_ONLY = false, bool QX = false>
+static constexpr auto ksc() { return &k_select_clusters<PHASE, CAP, LISTED, TPB, SHORT_ONLY, LONG, QX>; }
 
 template <bool LONG>
 static int launch_select_clusters_t(apples_ctx *ctx, const SelectArgs &a, int64_t nq) {
     if (nq == 0) return 0;
-    if constexpr (!LONG)  // panels with bytes beyond ACGT- held as gaps: the survivors' true counts, the rule once more
-        if (a.ex_mmax && a.cl_xoff) {  // (a.seg_slot / a.seg_cnt are the workspace's: the kernel rewrites them through its own pointers)
+    const bool qx = !LONG && a.qx_idx != nullptr;  // the block's queries hold such bytes too: the kernels' QX forms
+    if (qx && (LONG || !a.qx || !a.qpacked8 || !a.packed8 || !a.ex_mmax || !a.rep_panel || a.G > 64)) {
+        ctx->err = "k_cluster_rep_query_fix: needs the 8-plane forms of the block and of the reference in a context of fewer than 8 192 sites";
+        return 1;
+    }
+    if constexpr (!LONG) {  // panels with bytes beyond ACGT- held as gaps: the survivors' true counts, the rule once more
+        if (qx) {
+            const size_t dyn_fix = (size_t)a.G * 10 * sizeof(uint4);  // (G <= 64: 10 KB at the most)
+            hipLaunchKernelGGL(k_cluster_rep_query_fix, dim3((unsigned)nq), dim3(APPLES_TPB), dyn_fix, ctx->stream, a, ctx->ws.seg_slot, ctx->ws.seg_cnt);
+            HIP_TRY(ctx, hipGetLastError());
+        } else if (a.ex_mmax && a.cl_xoff) {  // (a.seg_slot / a.seg_cnt are the workspace's: the kernel rewrites them through its own pointers)
             hipLaunchKernelGGL(k_cluster_rep_fix, dim3((unsigned)nq), dim3(APPLES_TPB), 0, ctx->stream, a, ctx->ws.seg_slot, ctx->ws.seg_cnt);
             HIP_TRY(ctx, hipGetLastError());
         }
+    }
     // the slot bitmap and its 16-bit in-run prefixes (runs of 16 words: 262 144 slots); with clade blocks over emission indices
     size_t dyn = (size_t)(((a.e_of_slot ? std::max(a.n_e, a.n_members) : a.n_members) + 63) >> 6) * 10;
     if (a.e_of_slot) dyn = std::max<size_t>(dyn, 1024 * 16 + (SELECT_CLUSTERS_ACC_CAP + 1) * 4);  // (the short form's list lives in the bitmap's memory)
@@ -1901,6 +2196,14 @@ static int launch_select_clusters_t(apples_ctx *ctx, const SelectArgs &a, int64_
     }
     if (sd && !a.cl_count) { ctx->err = "scoredist cluster route without its tile scratch"; return 1; }
     if (by_query || !a.cl_count) {
+        if constexpr (!LONG)
+            if (qx) {
+                constexpr auto k0 = ksc<false, 0, SELECT_CLUSTERS_ACC_CAP, false, APPLES_TPB, false, true>();
+                if (dyn > 48 * 1024) HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(k0), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
+                hipLaunchKernelGGL(k0, dim3((unsigned)nq), dim3(APPLES_TPB), dyn, ctx->stream, a);
+                HIP_TRY(ctx, hipGetLastError());
+                return 0;
+            }
         hipLaunchKernelGGL((ksc<LONG, 0>()), dim3((unsigned)nq), dim3(APPLES_TPB), dyn, ctx->stream, a);
         HIP_TRY(ctx, hipGetLastError());
         return 0;
@@ -1926,6 +2229,25 @@ static int launch_select_clusters_t(apples_ctx *ctx, const SelectArgs &a, int64_
     }
     const int per_cu = (int)knob(ctx, "APPLES_CLUSTER_WGS", 8);  // tuning knob
     if (sd) hipLaunchKernelGGL(k_cluster_dist_sd<4>, dim3((unsigned)(ctx->n_cu * std::max(per_cu, 1))), dim3(APPLES_TPB), 0, ctx->stream, a);
+    else if (qx) {
+        // the tiles of clean queries on the matrix cores as ever (the QX instantiations pass over the others), then the bit-count QX
+        // form for the tiles that hold a flagged query -- for every tile without the matrix-core form
+        if constexpr (!LONG) {
+            if (a.cl_mfma) {
+                hipLaunchKernelGGL((k_cluster_dist_mfma<false, false, 1>), dim3((unsigned)(ctx->n_cu * 4 * CLM_WAVES)), dim3(WAVE), 0, ctx->stream, a);
+                HIP_TRY(ctx, hipGetLastError());
+                if (a.cl_xoff) {
+                    hipLaunchKernelGGL((k_cluster_dist_mfma<false, true, 1>), dim3((unsigned)(ctx->n_cu * 4 * CLM_EX_WAVES)), dim3(WAVE), 0, ctx->stream, a);
+                    HIP_TRY(ctx, hipGetLastError());
+                }
+                if (a.qx_mfma) {  // the tiles that hold a flagged query: the matrix-core QX form
+                    hipLaunchKernelGGL((k_cluster_dist_mfma<false, true, 2>), dim3((unsigned)(ctx->n_cu * 4 * CLM_EX_WAVES)), dim3(WAVE), 0, ctx->stream, a);
+                    HIP_TRY(ctx, hipGetLastError());
+                }
+            }
+            if (!(a.cl_mfma && a.qx_mfma == 2)) hipLaunchKernelGGL(k_cluster_dist_qx, dim3((unsigned)(ctx->n_cu * std::max(per_cu, 1))), dim3(APPLES_TPB), 0, ctx->stream, a);
+        }
+    }
     else if (a.cl_mfma) {
         hipLaunchKernelGGL(k_cluster_dist_mfma<LONG>, dim3((unsigned)(ctx->n_cu * 4 * (LONG ? 1 : CLM_WAVES))), dim3(WAVE), 0, ctx->stream, a);  // (18 KB of LDS per wavefront: eight per CU)
         if (a.cl_xoff) {  // the tiles of the clusters with bytes beyond ACGT- (the launch above passed over them)
@@ -2002,10 +2324,14 @@ int launch_select_clusters_listed(apples_ctx *ctx, const SelectArgs &a, int64_t 
         b.rep_cache = 0;
         dyn = (n_words + (n_words + 3) / 4) * 8;
     }
-    const void *fn = a.cl_long ? reinterpret_cast<const void *>(ksc<true, 4>()) : reinterpret_cast<const void *>(ksc<false, 4>());
+    constexpr auto k4qx = ksc<false, 4, SELECT_CLUSTERS_ACC_CAP, true, APPLES_TPB, false, true>();  // (the block's queries hold bytes beyond ACGT-)
+    const bool qx = !a.cl_long && a.qx_idx != nullptr;
+    const void *fn = a.cl_long ? reinterpret_cast<const void *>(ksc<true, 4>())
+                               : (qx ? reinterpret_cast<const void *>(k4qx) : reinterpret_cast<const void *>(ksc<false, 4>()));
     if (dyn > 48 * 1024)  // (beyond the default allowance of dynamic LDS; per device, so asked for at every launch)
         HIP_TRY(ctx, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
-    if (a.cl_long) hipLaunchKernelGGL((ksc<true, 4>()), dim3((unsigned)std::min<int64_t>(nq_max, 1024)), dim3(APPLES_TPB), dyn, ctx->stream, b);
+    if (qx) hipLaunchKernelGGL(k4qx, dim3((unsigned)std::min<int64_t>(nq_max, 1024)), dim3(APPLES_TPB), dyn, ctx->stream, b);
+    else if (a.cl_long) hipLaunchKernelGGL((ksc<true, 4>()), dim3((unsigned)std::min<int64_t>(nq_max, 1024)), dim3(APPLES_TPB), dyn, ctx->stream, b);
     else hipLaunchKernelGGL((ksc<false, 4>()), dim3((unsigned)std::min<int64_t>(nq_max, 1024)), dim3(APPLES_TPB), dyn, ctx->stream, b);
     HIP_TRY(ctx, hipGetLastError());
     return 0;
